@@ -269,3 +269,23 @@ def test_kfd_queue_sampler_reads_sysfs(tmp_path, monkeypatch):
     assert "error" in qs.result()
     out = bench.run_single_process([0, 1], [0, 1], timeout=30, child_cmd=lambda m, d: ["true"])
     assert "queues_per_gpu" in out["host"] and "queues_per_gpu" in out["rccl"]
+
+
+def test_dump_outputs_holds_u64_answers_exactly(tmp_path):
+    """--dump-outputs: result.npy / ranks.npy are float64 arrays of the
+    answers' 32-bit words, so u64 values above 2^53 survive exactly."""
+    import numpy as np
+    res = (bench.MAXU64 - 1, (1 << 63) + 12345)
+    answers = [{"hash": res[0], "nonce": res[1]}, {"hash": 5256245051, "nonce": 1626825724}]
+    out = tmp_path / "a" / "b"  # made if missing
+    bench.dump_outputs(str(out), res, answers)
+    assert sorted(p.name for p in out.iterdir()) == ["ranks.npy", "result.npy"]
+    r, rk = np.load(out / "result.npy"), np.load(out / "ranks.npy")
+    assert r.dtype == np.float64 and r.shape == (4,)
+    assert rk.dtype == np.float64 and rk.shape == (2, 4)
+
+    def back(w):
+        return (int(w[0]) << 32 | int(w[1]), int(w[2]) << 32 | int(w[3]))
+    assert back(r) == res and back(rk[0]) == res
+    assert back(rk[1]) == (5256245051, 1626825724)
+    assert float(r.max()) < 2.0 ** 32

@@ -63,7 +63,7 @@ def test_bench_torchrun_gloo_two_ranks_cfg2_and_cfg4():
     """Also the multi-rank single-process pass: rank 1 parks in the host-side
     wait group while rank 0 runs both children (HM_BENCH_SP_DEVICES=0: one
     context on GPU 0, host merge and a 1-rank RCCL merge)."""
-    line = _torchrun(2, ["--steps", "1", "--warmup", "0", "--secondary", "cfg4",
+    line = _torchrun(2, ["--full", "--steps", "1", "--warmup", "0", "--secondary", "cfg4",
                          "--no-cpu-baseline"],
                      {"HM_BENCH_BACKEND": "gloo", "HM_BENCH_SP_DEVICES": "0"}, timeout=600)
     assert line["n_gpus"] == 2 and line["config"]["merge"] == "gloo"
@@ -105,7 +105,7 @@ def test_bench_torchrun_gloo_two_ranks_cfg2_and_cfg4():
 
 
 def test_bench_torchrun_rccl_world1_cfg2_and_cfg3():
-    line = _torchrun(1, ["--steps", "2", "--warmup", "1", "--secondary", "cfg3",
+    line = _torchrun(1, ["--full", "--steps", "2", "--warmup", "1", "--secondary", "cfg3",
                          "--no-cpu-baseline"], {"HM_BENCH_FORCE_DIST": "1"}, timeout=300)
     assert line["config"]["merge"] == "RCCL all-gather"
     assert line["result_vs_oracle"]["match"] is True, line["result_vs_oracle"]
@@ -130,7 +130,7 @@ def test_bench_torchrun_rccl_all_visible_gpus():
     n = min(torch.cuda.device_count(), 8)
     if n < 2:
         pytest.skip(f"{n} visible GPU(s): the RCCL launch line needs >= 2")
-    line = _torchrun(n, ["--steps", "2", "--warmup", "1", "--secondary", "cfg4",
+    line = _torchrun(n, ["--full", "--steps", "2", "--warmup", "1", "--secondary", "cfg4",
                          "--no-cpu-baseline"], {}, timeout=600)
     assert line["n_gpus"] == n and line["config"]["merge"] == "RCCL all-gather"
     assert line["result_vs_oracle"]["match"] is True, line["result_vs_oracle"]
@@ -164,7 +164,7 @@ def test_bench_single_process_workload_on_one_gpu():
     driver launches bench.py (torch.distributed.run, RCCL process group at
     world size 1 via HM_BENCH_FORCE_DIST), so the host-side (gloo) wait group
     the other ranks park on is created and used too."""
-    line = _torchrun(1, ["--steps", "1", "--warmup", "0", "--secondary", "cfg4",
+    line = _torchrun(1, ["--full", "--steps", "1", "--warmup", "0", "--secondary", "cfg4",
                          "--no-cpu-baseline"],
                      {"HM_BENCH_FORCE_DIST": "1", "HM_BENCH_SP_DEVICES": "0,0"}, timeout=500)
     assert line["config"]["merge"] == "RCCL all-gather"
@@ -179,3 +179,39 @@ def test_bench_single_process_workload_on_one_gpu():
         assert e["result_vs_oracle"]["match"] is True, e
         assert e["result"] == line["workloads"]["cfg4"]["result"]
         assert e["mid_call_syncs"] == 0 and e["value"] > 0 and e["child_s"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_answer(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times its K steps and
+    nothing else: no fixture checks, roofline, secondaries, queue counts or
+    CPU baseline in the line (those are --full's).  --dump-outputs writes the
+    last step's answer, equal here to large.json's configs[1] fixture."""
+    import numpy as np
+    out = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "0",
+                        "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode == 0, p.stderr[-4000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    line = json.loads(lines[0])
+    assert line["full"] is False and line["steps"] == 2 and line["warmup"] == 0
+    assert line["unit"] == "GH/s" and line["higher_is_better"] is True and line["dtype"] == "u32"
+    assert line["ms_per_step"] > 0
+    # value = nonces of the timed steps / their time
+    assert abs(line["value"] - 2**32 / (line["ms_per_step"] * 1e-3) / 1e9) < 0.01 * line["value"]
+    assert len(line["ranks"]["local_ms"]) == 1 and line["build_matches_tree"] is True
+    for k in ("workloads", "cpu_baseline", "single_process"):
+        assert k not in line, k
+    for k in ("roofline", "result_vs_oracle", "all_ranks_match", "queues_per_gpu"):
+        assert line[k] is None, k
+    assert line["ranks"]["match"] == [None]
+    with open(os.path.join(ROOT, "tests", "golden", "large.json")) as f:
+        c2 = next(c for c in json.load(f) if bytes.fromhex(c["msg_hex"]) == b"bradfitz")
+    h, n = int(c2["hash"]), int(c2["nonce"])
+    exp = np.array([h >> 32, h & 0xFFFFFFFF, n >> 32, n & 0xFFFFFFFF], dtype=np.float64)
+    assert sorted(f.name for f in out.iterdir()) == ["ranks.npy", "result.npy"]
+    res, rk = np.load(out / "result.npy"), np.load(out / "ranks.npy")
+    assert res.dtype == np.float64 and np.array_equal(res, exp)
+    assert rk.dtype == np.float64 and np.array_equal(rk, exp[None, :])
+    assert line["result"] == {"hash": h, "nonce": n}
