@@ -1,4 +1,5 @@
-"""ctypes binding of libhipminer.so (include/hipminer.h).
+"""ctypes binding of libhipminer.so (include/hipminer.h; the test hooks and
+debug exports of include/hipminer_debug.h).
 
 The library is built in-tree by ``__graft_entry__.build()`` (or ``make -C
 distributed_bitcoinminer_amd/csrc``).  There is no silent fallback: if the
@@ -36,9 +37,7 @@ HM_OPT_FUSED_PARTS = 12
 HM_OPT_DEADLINE_MS = 13
 HM_OPT_FUSED_TAIL = 14
 HM_OPT_TAIL_FUSED = 15
-HM_OPT_HOST_RESULT = 16
 HM_OPT_QUEUE_BATCH = 17
-HM_OPT_FUSED_TRACE = 18
 HM_MERGE_NONE, HM_MERGE_HOST, HM_MERGE_RCCL = 0, 1, 2
 
 
@@ -136,9 +135,6 @@ def load() -> ctypes.CDLL:
         lib.hm_debug_auto_deadline_ms.restype = ctypes.c_double
         lib.hm_debug_auto_deadline_ms.argtypes = [u8p, ctypes.c_size_t, ctypes.c_uint64,
                                                   ctypes.c_uint64, ctypes.c_int]
-        lib.hm_debug_fused_trace.restype = ctypes.c_int
-        lib.hm_debug_fused_trace.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
-                                             ctypes.c_int]
         lib.hm_debug_streams_made.restype = ctypes.c_int
         lib.hm_debug_streams_made.argtypes = [ctypes.c_void_p, ctypes.c_int]
         lib.hm_debug_plan.restype = ctypes.c_int
@@ -225,15 +221,6 @@ class Context:
         device_index-th device (debug export; ABI 1.8 makes them on first use)."""
         return int(self._lib.hm_debug_streams_made(self._h, device_index))
 
-    def fused_trace(self) -> list:
-        """The last traced fused launch's timeline (HM_OPT_FUSED_TRACE):
-        per wave slot (start, last task start, end, tasks), wall-clock ticks."""
-        buf = (ctypes.c_uint64 * (4 * 32768))()
-        n = self._lib.hm_debug_fused_trace(self._h, buf, 32768)
-        if n < 0:
-            raise HipMinerError(n, "hm_debug_fused_trace")
-        return [tuple(int(x) for x in buf[4 * i: 4 * i + 4]) for i in range(n)]
-
     def set_option(self, opt: int, value: int) -> None:
         rc = self._lib.hm_set_option(self._h, opt, value)
         if rc != HM_OK:
@@ -297,7 +284,7 @@ def build_id() -> str:
 
 def build_matches_tree() -> bool:
     """True when the loaded libhipminer.so was built from this tree's sources
-    (build_id.tree_digest over csrc/ and include/hipminer.h)."""
+    (build_id.tree_digest over csrc/ and the headers under include/)."""
     from distributed_bitcoinminer_amd import build_id as bid
     return build_id() == bid.tree_digest()
 

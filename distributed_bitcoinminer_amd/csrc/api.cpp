@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/hipminer.h"
+#include "../../include/hipminer_debug.h"
 #include "build_id.h"  // generated: HM_BUILD_ID (distributed_bitcoinminer_amd/build_id.py)
 #include "kernels.hpp"
 #include "plan.hpp"
@@ -120,10 +121,7 @@ struct Device {
     uint64_t* best = nullptr;      // [kMaxBatch][kStreams][2]: per request, per stream
     uint64_t* result = nullptr;    // [kMaxBatch][2]
     uint64_t* gathered = nullptr;  // [ndev][kMaxBatch][2] (RCCL merge)
-    uint64_t* trace = nullptr;     // HM_OPT_FUSED_TRACE: 4 x u64 per wave slot of a fused launch
-    int trace_waves = 0;           // wave slots of the last traced fused launch
     hm_result* host_out = nullptr; // pinned, fine-grained [kMaxBatch]: the 16-B readback slots
-    uint64_t* host_dev = nullptr;  // host_out as the device addresses it
     hipEvent_t join[kStreams] = {};
     hipEvent_t gate = nullptr;     // stream 0 reached its last dominant segment
     hipEvent_t t0 = nullptr;       // timing origin of the current call
@@ -169,12 +167,7 @@ struct hm_ctx {
     uint32_t fused_parts = kFusedDefaultParts;  // HM_OPT_FUSED_PARTS (experiment hook)
     uint32_t fused_tail = kFusedDefaultTail;    // HM_OPT_FUSED_TAIL (1 = no split)
     bool tail_fused = true;  // HM_OPT_TAIL_FUSED: a large request's tail segments in one fused launch
-    // HM_OPT_HOST_RESULT (experiment hook, off): results stored to pinned host
-    // memory by the last fold instead of a 16-B copy -- measured no faster
-    // (config 1: 0.3591 vs 0.3595 ms, profiles/r06/experiments/host_result/)
-    bool host_result = false;
     int queue_batch = 0;     // HM_OPT_QUEUE_BATCH: 0 = auto, else tasks per queue atomic (4..32)
-    bool fused_trace = false; // HM_OPT_FUSED_TRACE (diagnostics): fused waves record their timeline
     // host waits on GPU work while the call is still enqueuing (hm_stats.mid_call_syncs)
     bool enqueuing = false;
     int32_t mid_syncs = 0;
@@ -246,11 +239,9 @@ int device_init(Device& dv, int ordinal) {
     HIPCHK(hipMalloc(&dv.best, (size_t)kMaxBatch * kStreams * 2 * sizeof(uint64_t)));
     HIPCHK(hipMalloc(&dv.acc, (size_t)kStreams * 2 * sizeof(uint64_t)));
     HIPCHK(hipMalloc(&dv.result, (size_t)kMaxBatch * 2 * sizeof(uint64_t)));
-    // fine-grained (coherent) pinned memory: the last fold kernel of a call
-    // stores the results here with system-scope stores (HM_OPT_HOST_RESULT)
+    // pinned readback slots of the 16-B result copies
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&dv.host_out), kMaxBatch * sizeof(hm_result),
                          hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&dv.host_dev), dv.host_out, 0));
     return HM_OK;
 }
 
@@ -282,7 +273,6 @@ void device_free(Device& dv) {
     if (dv.acc) (void)hipFree(dv.acc);
     if (dv.result) (void)hipFree(dv.result);
     if (dv.gathered) (void)hipFree(dv.gathered);
-    if (dv.trace) (void)hipFree(dv.trace);
     if (dv.host_out) (void)hipHostFree(dv.host_out);
     dv.ordinal = -1;
 }
@@ -757,7 +747,7 @@ int fused_rank(const SegPlan& g) {
 // -> hm_fold_kernel into *best.  Tasks are ordered costliest layout first,
 // larger segments first.
 int enqueue_fused(hm_ctx* ctx, Device& dv, const MsgPlan& mp, std::vector<SegPlan> segs, int si,
-                  uint64_t* best, bool seed_best, uint64_t* host = nullptr) {
+                  uint64_t* best, bool seed_best) {
     hipStream_t st = dv.stream[si];
     std::stable_sort(segs.begin(), segs.end(), [](const SegPlan& a, const SegPlan& b) {
         if (fused_rank(a) != fused_rank(b)) return fused_rank(a) < fused_rank(b);
@@ -896,11 +886,6 @@ int enqueue_fused(hm_ctx* ctx, Device& dv, const MsgPlan& mp, std::vector<SegPla
     }
     fa.ntasks = (uint32_t)ids;
     fa.nbig = (uint32_t)nbig;
-    if (ctx->fused_trace) {
-        if (!dv.trace)
-            HIPCHK(hipMalloc(&dv.trace, (size_t)kMaxCandWaves * 4 * sizeof(uint64_t)));
-        fa.trace = dv.trace;
-    }
     fa.nparts = nparts > 1 ? nparts : 1;
     fa.nseg = pa.nseg = (uint32_t)segs.size();
     pa.njobs = (uint32_t)jobs;
@@ -914,7 +899,6 @@ int enqueue_fused(hm_ctx* ctx, Device& dv, const MsgPlan& mp, std::vector<SegPla
     // with static first tasks the queue starts past every wave slot
     pa.counter0 = (fa.flags & kFusedStaticFirst) ? (uint32_t)grid * (kBlock / kWaveSize) : 0;
     HIPCHK(launch_fused_plan(pa, st));
-    if (fa.trace) dv.trace_waves = grid * (kBlock / kWaveSize);
     Launch L;
     rc = next_event(dv, &L.start);
     if (rc) return rc;
@@ -930,7 +914,7 @@ int enqueue_fused(hm_ctx* ctx, Device& dv, const MsgPlan& mp, std::vector<SegPla
     rc = launch_scan(*fn, fa, grid, st);
     if (rc) return rc;
     HIPCHK(hipEventRecord(L.stop, st));
-    HIPCHK(launch_fold(dv.cand[si], (uint32_t)grid * (kBlock / kWaveSize), best, st, 1, host));
+    HIPCHK(launch_fold(dv.cand[si], (uint32_t)grid * (kBlock / kWaveSize), best, st));
     if (ctx->csum)
         HIPCHK(launch_sum_fold(dv.sums[si], (uint32_t)grid * (kBlock / kWaveSize), dv.acc + 2 * si,
                                st));
@@ -945,13 +929,10 @@ struct DevReq {
 };
 
 // Enqueue a batch of scans on one device; request r's result lands in
-// dv.result + 2r, and with `to_host` also in the pinned readback slot
-// dv.host_out[r] (stored by the last fold kernel).  All segments of all
-// requests are queued before any sync.  `first`: the call's first chunk,
-// which records the timing origin dv.t0 (every launch of an hm_scan_many
-// call is timed against it).
-int enqueue_device_batch(hm_ctx* ctx, Device& dv, const std::vector<DevReq>& reqs, bool first,
-                         bool to_host) {
+// dv.result + 2r.  All segments of all requests are queued before any sync.
+// `first`: the call's first chunk, which records the timing origin dv.t0
+// (every launch of an hm_scan_many call is timed against it).
+int enqueue_device_batch(hm_ctx* ctx, Device& dv, const std::vector<DevReq>& reqs, bool first) {
     HIPCHK(hipSetDevice(dv.ordinal));
     const int n = (int)reqs.size();
     hipStream_t s0 = dv.stream[0];
@@ -963,8 +944,7 @@ int enqueue_device_batch(hm_ctx* ctx, Device& dv, const std::vector<DevReq>& req
         std::vector<SegPlan> segs = plan_range(*reqs[0].mp, reqs[0].lo, reqs[0].hi,
                                                ctx->force_generic, ctx->table_digits);
         if (fusible(segs))
-            return enqueue_fused(ctx, dv, *reqs[0].mp, segs, 0, dv.result, true,
-                                 to_host ? dv.host_dev : nullptr);
+            return enqueue_fused(ctx, dv, *reqs[0].mp, segs, 0, dv.result, true);
     }
     // streams == 1: every segment in order on stream 0, so kernels never
     // overlap and per-kernel timings match rocprofv3 exactly.  streams > 1:
@@ -1103,8 +1083,7 @@ int enqueue_device_batch(hm_ctx* ctx, Device& dv, const std::vector<DevReq>& req
         HIPCHK(hipStreamWaitEvent(s0, dv.join[s], 0));
     }
     for (int r = 0; r < n; ++r)
-        HIPCHK(launch_fold(dv.best + (size_t)r * kStreams * 2, kStreams, dv.result + 2 * r, s0, 1,
-                           to_host ? dv.host_dev + 2 * r : nullptr));
+        HIPCHK(launch_fold(dv.best + (size_t)r * kStreams * 2, kStreams, dv.result + 2 * r, s0));
     return HM_OK;
 }
 
@@ -1153,7 +1132,7 @@ int rccl_merge(hm_ctx* ctx, int nreq) {
     HIPCHK(launch_init_best(d0.result, (uint32_t)nreq, d0.stream[0]));
     for (int r = 0; r < nreq; ++r)
         HIPCHK(launch_fold(d0.gathered + 2 * r, (uint32_t)n, d0.result + 2 * r, d0.stream[0],
-                           (uint32_t)nreq, ctx->host_result ? d0.host_dev + 2 * r : nullptr));
+                           (uint32_t)nreq));
     return HM_OK;
 }
 
@@ -1184,8 +1163,7 @@ int scan_chunk(hm_ctx* ctx, const hm_request* reqs, int nreq, hm_result* outs, b
     const auto te = std::chrono::steady_clock::now();
     ctx->enqueuing = true;
     for (int i = 0; i < ndev; ++i) {
-        int rc = enqueue_device_batch(ctx, ctx->devs[i], per_dev[i], first,
-                                      ctx->host_result && !ctx->merge_rccl);
+        int rc = enqueue_device_batch(ctx, ctx->devs[i], per_dev[i], first);
         if (rc) { ctx->enqueuing = false; return rc; }
     }
     ctx->enqueuing = false;
@@ -1197,9 +1175,8 @@ int scan_chunk(hm_ctx* ctx, const hm_request* reqs, int nreq, hm_result* outs, b
         ctx->merge = HM_MERGE_RCCL;
         Device& d0 = ctx->devs[0];
         HIPCHK(hipSetDevice(d0.ordinal));
-        if (!ctx->host_result)
-            HIPCHK(hipMemcpyAsync(d0.host_out, d0.result, nreq * sizeof(hm_result),
-                                  hipMemcpyDeviceToHost, d0.stream[0]));
+        HIPCHK(hipMemcpyAsync(d0.host_out, d0.result, nreq * sizeof(hm_result),
+                              hipMemcpyDeviceToHost, d0.stream[0]));
         for (auto& dv : ctx->devs) {
             HIPCHK(hipSetDevice(dv.ordinal));
             int rc = host_wait(ctx, dv.stream[0]);
@@ -1210,7 +1187,6 @@ int scan_chunk(hm_ctx* ctx, const hm_request* reqs, int nreq, hm_result* outs, b
     }
     ctx->merge = ndev > 1 ? HM_MERGE_HOST : HM_MERGE_NONE;
     for (auto& dv : ctx->devs) {
-        if (ctx->host_result) break;  // the last fold stored them in host_out
         HIPCHK(hipSetDevice(dv.ordinal));
         HIPCHK(hipMemcpyAsync(dv.host_out, dv.result, nreq * sizeof(hm_result),
                               hipMemcpyDeviceToHost, dv.stream[0]));
@@ -1244,8 +1220,11 @@ uint64_t hm_hash(const uint8_t* msg, size_t len, uint64_t nonce) {
 // 1.6: hm_build_id, hm_stats.enqueue_ms / mid_call_syncs / table_grows, HM_OPT_TABLE_ROWS_CAP;
 // 1.7: hm_scan_cpu, hm_scan_stats frozen at HM_STATS_SIZE_1_4 bytes;
 // 1.8: HM_OPT_DEADLINE_MS / HM_ERR_TIMEOUT, hm_stats.deadline_ms, streams 1..
-//      made on first use
-int hm_version(void) { return (1 << 16) | 8; }
+//      made on first use;
+// 1.9: option ids 16 and 18 (rejected experiment hooks) retired:
+//      hm_set_option answers HM_ERR_INVALID; the wave-timeline debug export removed;
+//      test and experiment hooks and hm_debug_* prototypes moved to hipminer_debug.h
+int hm_version(void) { return (1 << 16) | 9; }
 
 // The digest of the sources this library was built from (build_id.py), kept
 // in the binary behind a tag so tools can read it without loading the library.
@@ -1382,16 +1361,10 @@ int hm_set_option(hm_ctx* ctx, int opt, int64_t value) {
             if (value != 1 && value != 2 && value != 5 && value != 10) return HM_ERR_INVALID;
             ctx->fused_parts = (uint32_t)value;
             return HM_OK;
-        case HM_OPT_FUSED_TRACE:
-            ctx->fused_trace = value != 0;
-            return HM_OK;
         case HM_OPT_QUEUE_BATCH:
             if (value != 0 && value != 4 && value != 8 && value != 16 && value != 32)
                 return HM_ERR_INVALID;
             ctx->queue_batch = (int)value;
-            return HM_OK;
-        case HM_OPT_HOST_RESULT:
-            ctx->host_result = value != 0;
             return HM_OK;
         case HM_OPT_TAIL_FUSED:
             ctx->tail_fused = value != 0;
@@ -1609,28 +1582,12 @@ int hm_scan_stats_sized(const hm_ctx* ctx, hm_stats* out, size_t size) {
     return HM_OK;
 }
 
-// ---- debug exports for host-side tests (not part of include/hipminer.h) ----
+// ---- debug exports for host-side tests (include/hipminer_debug.h) ----
 // The embedded scan code object (scan_blob.S): bench.py hashes these bytes to
 // match a PMC summary to the build that actually runs.
 size_t hm_debug_code_object(const unsigned char** p) {
     if (p) *p = hm_scan_code_object;
     return (size_t)(hm_scan_code_object_end - hm_scan_code_object);
-}
-
-// The timeline of the last traced fused launch on device 0 (HM_OPT_FUSED_TRACE):
-// up to `cap` wave slots x 4 u64 -- wall_clock64 at the wave's start, at its
-// last task's start, at its end, and its task count.  Returns the launch's
-// wave slots (0: none traced).  Diagnostics (tools/fused_trace.py).
-int hm_debug_fused_trace(hm_ctx* ctx, uint64_t* out, int cap) {
-    if (!ctx || !out || cap < 0) return HM_ERR_INVALID;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if (ctx->abandoned) return HM_ERR_TIMEOUT;
-    Device& dv = ctx->devs[0];
-    if (!dv.trace || !dv.trace_waves) return 0;
-    HIPCHK(hipSetDevice(dv.ordinal));
-    const int n = std::min(cap, dv.trace_waves);
-    int rc = host_read(ctx, out, dv.trace, (size_t)n * 4 * sizeof(uint64_t));
-    return rc ? rc : dv.trace_waves;
 }
 
 // HM_OPT_DEADLINE_MS = -1's deadline for one request on `cus` compute units

@@ -150,14 +150,14 @@ struct FusedSeg {
     uint32_t d, nb;       // generic: digits, tail blocks
 };
 
-// FusedArgs::flags (HM_OPT_FUSED_FLAGS): how waves get their tasks
+// FusedArgs::flags (HM_OPT_FUSED_FLAGS, hipminer_debug.h): how waves get their tasks
 constexpr uint32_t kFusedStaticFirst = 1;  // first task = the wave's slot; the counter starts past them
 constexpr uint32_t kFusedPrefetch = 2;     // dequeue the next task id while running the current one
 constexpr uint32_t kFusedStatic = 4;       // no queue: wave w runs tasks w, w + nwaves, w + 2 nwaves, ...
 constexpr uint32_t kFusedLds = 8;          // dequeue through the workgroup's LDS dispenser (scan_tasks.hpp)
 // the SIMD's arbiter issues from the oldest wave first, so the youngest waves
 // of a SIMD hold their first task for most of a small launch and finish it
-// alone at the end (tools/fused_trace.py): with kFusedPrioEq a wave's
+// alone at the end (profiles/r06/experiments/fused_timeline/): with kFusedPrioEq a wave's
 // priority (s_setprio) falls with the tasks it has run, 3, 2, 1, 0, so the
 // waves of a SIMD progress together
 constexpr uint32_t kFusedPrioEq = 16;
@@ -180,9 +180,11 @@ struct FusedArgs {
     uint32_t r;           // prefix-remainder bytes (generic)
     uint32_t pw[16];      // prefix remainder words (generic)
     uint32_t mid[8];      // midstate (generic)
-    // diagnostics (HM_OPT_FUSED_TRACE): per wave slot w, [4w..4w+3] = the
-    // constant-rate wall clock (wall_clock64) at the wave's start, when it
-    // takes its last task, at its end, and the tasks it ran; null = off
+    // wave-timeline diagnostics of ABI 1.8: per wave slot w, [4w..4w+3] = the
+    // wall clock at the wave's start, when it takes its last task, at its
+    // end, and the tasks it ran.  Always null since ABI 1.9 (the host side is
+    // gone); the field and the kernel's reads of it leave with the next
+    // change to the fused kernel
     uint64_t* trace;
     FusedSeg segs[kMaxFusedSegs];
 };
@@ -222,10 +224,9 @@ hipError_t launch_sum_fold(const uint64_t* sums, uint32_t n, uint64_t* acc, hipS
 hipError_t launch_kw_table(uint32_t* out, uint32_t f, uint32_t fe, uint64_t base,
                            uint64_t total_bits, hipStream_t s);
 // Fold n (key, nonce) pairs (pair i at cand + 2*i*stride) plus *best into
-// *best (lexicographic min); with `host` (pinned fine-grained host memory)
-// the result is also written there, system-scope.
+// *best (lexicographic min).
 hipError_t launch_fold(const uint64_t* cand, uint32_t n, uint64_t* best, hipStream_t s,
-                       uint32_t stride = 1, uint64_t* host = nullptr);
+                       uint32_t stride = 1);
 hipError_t launch_init_best(uint64_t* best, uint32_t n, hipStream_t s);
 // The fused launch's planner: tile records, tables, counter/result/acc reset.
 hipError_t launch_fused_plan(const FusedPlanArgs& a, hipStream_t s);

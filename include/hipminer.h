@@ -153,7 +153,10 @@ typedef struct hm_stats {
 #define HM_KIND_FUSED 4    /* every segment of a small request in one launch, each
                               with its own layout's task body (ABI 1.7)          */
 
-/* Options for hm_set_option. */
+/* Options for hm_set_option (test and experiment hooks: hipminer_debug.h).
+ * Ids 16 and 18 are retired and never reused.  ABI 1.9: hm_set_option
+ * returns HM_ERR_INVALID for a retired id at any value and changes nothing;
+ * the context stays usable.  A caller that set one may drop the call. */
 #define HM_OPT_FORCE_GENERIC 1 /* 1: route every segment to the generic kernel  */
 #define HM_OPT_MERGE_RCCL 2    /* 1: merge the per-device candidates with one RCCL
                                   all-gather (also with one device: a 1-rank
@@ -171,40 +174,11 @@ typedef struct hm_stats {
                                   enqueues onto them: every HIP stream holds a
                                   hardware queue until the process exits, so a
                                   process sharing its GPU sets 1 or 2        */
-#define HM_OPT_TABLE_DIGITS 7  /* test hook (-1..7, 0 = default 7): the final-
-                                  block digits one K+W table of the chained
-                                  kernel covers; the remaining high final-block
-                                  digits run as epochs (one table each).  Smaller
-                                  values exercise the epochs on small ranges;
-                                  -1 keeps final blocks of >= 5 digits on the
-                                  tiled kernel (ABI 1.5)                        */
-#define HM_OPT_TABLE_ROWS_CAP 8 /* test hook (>= 0, 0 = off): a K+W table may not
-                                  grow beyond this many rows, as if the device
-                                  were out of memory; the chained layout then
-                                  falls back to smaller tables and more epochs
-                                  (the HM_ERR_NOMEM path of table growth; ABI
-                                  1.6)                                          */
-#define HM_OPT_TEST_MID_SYNC 9  /* test hook (0/1): the call waits on the host for
-                                  each device's first queued work while still
-                                  enqueuing, which hm_stats.mid_call_syncs must
-                                  count (ABI 1.7)                               */
 #define HM_OPT_FUSED 10         /* 1 (default): a request (per device shard) of at
                                   most 2^27 nonces whose segments all fit the
                                   fused launch runs as ONE planner + ONE scan
                                   launch (HM_KIND_FUSED); 0: one launch per
                                   digit segment (ABI 1.7)                       */
-#define HM_OPT_FUSED_FLAGS 11   /* experiment hook (0..31): how the fused launch's
-                                  waves get tasks -- bit 0: first task = the
-                                  wave's slot (no opening burst of queue
-                                  atomics); bit 1: dequeue the next task while
-                                  the current one runs; bit 2: no queue, wave
-                                  slots strided over the task ids; bit 3:
-                                  dequeue through the workgroup's LDS
-                                  dispenser (ABI 1.7); bit 4: a wave's priority
-                                  falls with the tasks it ran (ABI 1.8)         */
-#define HM_OPT_FUSED_PARTS 12   /* experiment hook (1, 2, 5, 10; default 1): a
-                                  tiled task of the fused launch covers 10 /
-                                  parts steps of its units loop (ABI 1.7)       */
 #define HM_OPT_DEADLINE_MS 13   /* ABI 1.8 (SURVEY §8(b) liveness): 0 (default) =
                                   a call blocks until its GPU work is done; > 0 =
                                   a call returns HM_ERR_TIMEOUT (and abandons the
@@ -231,19 +205,6 @@ typedef struct hm_stats {
                                   launch on a low-priority stream, in the
                                   dominant launch's tail, when they fit one; 0:
                                   one launch per segment on the tail streams */
-#define HM_OPT_HOST_RESULT 16   /* experiment hook (0/1, default 0; ABI 1.8): 1 =
-                                  the call's last fold kernel stores the 16-B
-                                  results into pinned host memory (system-scope
-                                  stores) instead of a hipMemcpyAsync readback;
-                                  measured no faster                            */
-#define HM_OPT_QUEUE_BATCH 17   /* experiment hook (0, 4, 8, 16, 32; ABI 1.8):
-                                  tasks a workgroup fetches per work-queue
-                                  atomic in the per-segment kernels; 0 (default)
-                                  = 4, and 16 for launches of >= 10^11 nonces */
-#define HM_OPT_FUSED_TRACE 18   /* diagnostics (0/1; ABI 1.8): fused launches on
-                                  device 0 record each wave's timeline
-                                  (tools/fused_trace.py)                        */
-
 /* bitcoin.Hash (hash.go:13-17) evaluated on the host.  Not the hot path: used
  * to verify single results and for planning; needs no GPU. */
 uint64_t hm_hash(const uint8_t *msg, size_t len, uint64_t nonce);
@@ -338,8 +299,8 @@ void hm_close(hm_ctx *ctx);
 int hm_version(void);
 
 /* Build identity (ABI 1.6): 16 hex digits of sha256 over the sources the
- * library was built from (distributed_bitcoinminer_amd/build_id.py: csrc/ and
- * this header, by path and content).  A caller holding the source tree can
+ * library was built from (distributed_bitcoinminer_amd/build_id.py: csrc/,
+ * this header and hipminer_debug.h, by path and content).  A caller holding the source tree can
  * check that the loaded library is that tree's build.  Static storage. */
 const char *hm_build_id(void);
 

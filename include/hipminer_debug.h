@@ -1,0 +1,78 @@
+/*
+ * hipminer_debug.h -- test hooks and debug exports of libhipminer.so.
+ *
+ * Not part of the drop-in boundary (hipminer.h): the suite and bench.py use
+ * these to reach paths a small range would not take and to look inside the
+ * library.  They may change with any ABI minor.
+ */
+#ifndef HIPMINER_DEBUG_H
+#define HIPMINER_DEBUG_H
+
+#include "hipminer.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Test and experiment hooks for hm_set_option (ids as they always were). */
+#define HM_OPT_TABLE_DIGITS 7  /* test hook (-1..7, 0 = default 7): the final-
+                                  block digits one K+W table of the chained
+                                  kernel covers; the remaining high final-block
+                                  digits run as epochs (one table each).  Smaller
+                                  values exercise the epochs on small ranges;
+                                  -1 keeps final blocks of >= 5 digits on the
+                                  tiled kernel (ABI 1.5)                        */
+#define HM_OPT_TABLE_ROWS_CAP 8 /* test hook (>= 0, 0 = off): a K+W table may not
+                                  grow beyond this many rows, as if the device
+                                  were out of memory; the chained layout then
+                                  falls back to smaller tables and more epochs
+                                  (the HM_ERR_NOMEM path of table growth; ABI
+                                  1.6)                                          */
+#define HM_OPT_TEST_MID_SYNC 9  /* test hook (0/1): the call waits on the host for
+                                  each device's first queued work while still
+                                  enqueuing, which hm_stats.mid_call_syncs must
+                                  count (ABI 1.7)                               */
+#define HM_OPT_FUSED_FLAGS 11   /* experiment hook (0..31, default 1): how the fused
+                                  launch's waves get tasks -- bit 0: first task =
+                                  the wave's slot (no opening burst of queue
+                                  atomics; the shipped scheme); bit 1: dequeue
+                                  the next task while the current one runs; bit
+                                  2: no queue, wave slots strided over the task
+                                  ids; bit 3: dequeue through the workgroup's
+                                  LDS dispenser (ABI 1.7); bit 4: a wave's
+                                  priority falls with the tasks it ran (ABI 1.8).
+                                  Bits 1..4 measured and rejected   */
+#define HM_OPT_FUSED_PARTS 12   /* experiment hook (1, 2, 5, 10; default 1): a
+                                  tiled task of the fused launch covers 10 /
+                                  parts steps of its units loop (ABI 1.7);
+                                  2, 5, 10 measured and rejected                */
+#define HM_OPT_QUEUE_BATCH 17   /* experiment hook (0, 4, 8, 16, 32; ABI 1.8):
+                                  tasks a workgroup fetches per work-queue
+                                  atomic in the per-segment kernels; 0 (default)
+                                  = 4, and 16 for launches of >= 10^11 nonces */
+
+/* The embedded scan code object: *p = its first byte, returns its size.
+ * bench.py hashes these bytes to match a PMC summary to the build that runs. */
+size_t hm_debug_code_object(const unsigned char **p);
+
+/* The deadline HM_OPT_DEADLINE_MS = -1 gives one request on `cus` compute
+ * units, in ms (-1.0 if planning failed).  Host-only. */
+double hm_debug_auto_deadline_ms(const uint8_t *msg, size_t len, uint64_t lo, uint64_t hi,
+                                 int cus);
+
+/* Streams (hardware queues) made so far on device i of ctx: 1 after hm_open,
+ * up to HM_OPT_STREAMS once calls used them; -1 if i is out of range. */
+int hm_debug_streams_made(const hm_ctx *ctx, int i);
+
+/* The planner's digit segments of [lo, hi] for msg: up to `cap` descriptors of
+ * 13 x int64 each -- d, lo, hi, kind, W1, V, trailer, straddle, seg_cost
+ * (SIMD cycles / 64 nonces), lane3, f, tch, fe (the last three chained only).
+ * Returns the number of segments (may exceed cap).  Host-only. */
+int hm_debug_plan(const uint8_t *msg, size_t len, uint64_t lo, uint64_t hi, int force_generic,
+                  int64_t *outv, int cap);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* HIPMINER_DEBUG_H */

@@ -47,6 +47,28 @@ def test_timeout_code_and_deadline_option_in_header():
     assert _lib.load().hm_set_option(None, _lib.HM_OPT_DEADLINE_MS, 5) == _lib.HM_ERR_INVALID
 
 
+def test_option_ids_match_headers_and_retired_ids_stay_out():
+    """ABI 1.9: every HM_OPT_* of include/hipminer.h (product options) and
+    include/hipminer_debug.h (test and experiment hooks) has an equal
+    constant in the binding and the binding has no other; the product header
+    defines no hook's id (7, 8, 9, 11, 12, 17) and neither header a retired
+    one (16, 18)."""
+    import re
+    inc = os.path.dirname(_lib.HEADER_PATH)
+    define = re.compile(r"^#define (HM_OPT_\w+) (\d+)\b", re.M)
+    product = {n: int(v) for n, v in define.findall(open(_lib.HEADER_PATH).read())}
+    debug = {n: int(v) for n, v in
+             define.findall(open(os.path.join(inc, "hipminer_debug.h")).read())}
+    assert product and debug and not set(product) & set(debug)
+    headers = {**product, **debug}
+    for name, value in headers.items():
+        assert getattr(_lib, name, None) == value, name
+    assert {n for n in vars(_lib) if n.startswith("HM_OPT_")} == set(headers)
+    assert not set(product.values()) & {7, 8, 9, 11, 12, 16, 17, 18}, product
+    assert not set(debug.values()) & {16, 18}, debug
+    assert _lib.load().hm_version() & 0xFFFF >= 9
+
+
 def test_hm_hash_matches_golden(golden):
     for k in golden["hash_kats"]:
         m = bytes.fromhex(k["msg_hex"])

@@ -241,11 +241,10 @@ def test_large_request_tail_segments_fused(ctx, oracle_mod):
     assert ctx.scan(bench.long120(), 0, 2**32 - 1) == (1410660608, 124104753)
 
 
-def test_results_stored_to_host_or_copied_agree(oracle_mod):
-    """HM_OPT_HOST_RESULT (round 6 experiment hook, default off): the call's
-    last fold kernel stores the 16-B results in pinned host memory instead of
-    the copy back.  Same answers on one device, a batch, a two-device host
-    merge and the RCCL merge, fused requests and a tail-fused one included."""
+def test_batch_and_single_results_agree_across_merges(oracle_mod):
+    """The 16-B results read back through the pinned slot: the same answers
+    from hm_scan_many and hm_scan on one device, a two-device host merge and
+    the RCCL merge, fused requests and a tail-fused one included."""
     # the last request has tail segments (d <= 8) that run as one fused
     # launch on a tail stream beside its dominant d = 9 launch
     reqs = [(b"bradfitz", 0, 10**7 + 1), (b"thom yorke", 10**9, 10**9 + 2 * 10**8),
@@ -262,26 +261,18 @@ def test_results_stored_to_host_or_copied_agree(oracle_mod):
         with _lib.Context(devs) as c:
             if rccl:
                 c.set_option(_lib.HM_OPT_MERGE_RCCL, 1)
-            for host in (1, 0, 1):
-                c.set_option(_lib.HM_OPT_HOST_RESULT, host)
-                assert c.scan_many(reqs) == exp, (devs, rccl, host)
-                for (m, a, b), e in zip(reqs, exp):
-                    assert c.scan(m, a, b) == e, (devs, rccl, host, m, a, b)
+            assert c.scan_many(reqs) == exp, (devs, rccl)
+            for (m, a, b), e in zip(reqs, exp):
+                assert c.scan(m, a, b) == e, (devs, rccl, m, a, b)
 
 
-def test_fused_trace_diagnostics(oracle_mod):
-    """HM_OPT_FUSED_TRACE (diagnostics, tools/fused_trace.py): every wave of the
-    fused launch records its start, last-task and end times and its task
-    count; the answers do not change and the waves' tasks cover the launch."""
-    with _lib.Context([0]) as c:
-        assert c.fused_trace() == []  # nothing traced yet
-        c.set_option(_lib.HM_OPT_FUSED_TRACE, 1)
-        assert c.scan(b"bradfitz", 0, 10**7 + 1) == (356393768206, 7645578)
-        tr = c.fused_trace()
-        st = c.stats()
-        assert len(tr) == st["dom_grid"] * 4, (len(tr), st)
-        assert all(t[0] <= t[1] <= t[2] for t in tr if t[3] > 0)
-        # 10^7 + 2 nonces: >= 15,625 tiled tasks of 640 nonces, plus pieces
-        assert sum(t[3] for t in tr) >= 15_625
-        m = b"z" * 120
-        assert c.scan(m, 0, 10**6) == oracle_mod.c_scan(m, 0, 10**6)
+def test_retired_options_are_refused(ctx):
+    """ABI 1.9: ids 16 and 18 (rejected experiment hooks) are refused and
+    leave the context as it was: config 1 is still one fused launch."""
+    for opt in (16, 18):
+        with pytest.raises(_lib.HipMinerError) as e:
+            ctx.set_option(opt, 1)
+        assert e.value.rc == _lib.HM_ERR_INVALID, opt
+    assert ctx.scan(b"bradfitz", 0, 10**7 + 1) == (356393768206, 7645578)
+    st = ctx.stats()
+    assert st["launches"] == 1 and st["dom_kind"] == _lib.HM_KIND_FUSED, st
