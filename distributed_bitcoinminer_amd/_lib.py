@@ -74,6 +74,18 @@ class hm_stats(ctypes.Structure):
         return d
 
 
+class hm_find_stats(ctypes.Structure):
+    """hm_find_stats of include/hipminer.h (ABI 1.10)."""
+    _fields_ = [("wall_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
+                ("nonces_enqueued", ctypes.c_uint64), ("tasks_total", ctypes.c_uint64),
+                ("tasks_run", ctypes.c_uint64), ("launches", ctypes.c_int32),
+                ("ndev", ctypes.c_int32), ("found", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -132,6 +144,17 @@ def load() -> ctypes.CDLL:
         lib.hm_scan_cpu.restype = ctypes.c_int
         lib.hm_scan_cpu.argtypes = [u8p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64,
                                     ctypes.c_int, ctypes.POINTER(hm_result)]
+        lib.hm_find.restype = ctypes.c_int
+        lib.hm_find.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint64,
+                                ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(hm_result),
+                                ctypes.POINTER(ctypes.c_int)]
+        lib.hm_find_cpu.restype = ctypes.c_int
+        lib.hm_find_cpu.argtypes = [u8p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64,
+                                    ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(hm_result),
+                                    ctypes.POINTER(ctypes.c_int)]
+        lib.hm_find_stats_sized.restype = ctypes.c_int
+        lib.hm_find_stats_sized.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_find_stats),
+                                            ctypes.c_size_t]
         lib.hm_debug_auto_deadline_ms.restype = ctypes.c_double
         lib.hm_debug_auto_deadline_ms.argtypes = [u8p, ctypes.c_size_t, ctypes.c_uint64,
                                                   ctypes.c_uint64, ctypes.c_int]
@@ -216,6 +239,27 @@ class Context:
             raise HipMinerError(rc, "hm_scan_stats")
         return st.as_dict()
 
+    def find(self, msg, lo: int, hi: int, target: int):
+        """hm_find (ABI 1.10): (hash, nonce) of the LOWEST nonce in the
+        inclusive [lo, hi] whose hash is below `target`, or None; the call
+        stops early once that nonce is known."""
+        m = as_bytes(msg)
+        out = hm_result()
+        found = ctypes.c_int(0)
+        rc = self._lib.hm_find(self._h, m, len(m), lo, hi, target, ctypes.byref(out),
+                               ctypes.byref(found))
+        if rc != HM_OK:
+            raise HipMinerError(rc, "hm_find")
+        return (int(out.hash), int(out.nonce)) if found.value else None
+
+    def find_stats(self) -> dict:
+        """hm_find_stats_sized: work accounting of the last find on this context."""
+        st = hm_find_stats()
+        rc = self._lib.hm_find_stats_sized(self._h, ctypes.byref(st), ctypes.sizeof(st))
+        if rc != HM_OK:
+            raise HipMinerError(rc, "hm_find_stats_sized")
+        return st.as_dict()
+
     def streams_made(self, device_index: int = 0) -> int:
         """HIP streams (hardware queues) the context has made on its
         device_index-th device (debug export; ABI 1.8 makes them on first use)."""
@@ -260,6 +304,18 @@ def scan_cpu(msg, lo: int, hi: int, threads: int = 0) -> tuple[int, int]:
     if rc != HM_OK:
         raise HipMinerError(rc, "hm_scan_cpu")
     return int(out.hash), int(out.nonce)
+
+
+def find_cpu(msg, lo: int, hi: int, target: int, threads: int = 0):
+    """hm_find_cpu (ABI 1.10): Context.find's answer on the host's cores."""
+    m = as_bytes(msg)
+    out = hm_result()
+    found = ctypes.c_int(0)
+    rc = load().hm_find_cpu(m, len(m), lo, hi, target, threads, ctypes.byref(out),
+                            ctypes.byref(found))
+    if rc != HM_OK:
+        raise HipMinerError(rc, "hm_find_cpu")
+    return (int(out.hash), int(out.nonce)) if found.value else None
 
 
 def partition(msg, lo: int, hi: int, n: int) -> list:

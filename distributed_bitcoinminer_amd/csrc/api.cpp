@@ -13,6 +13,7 @@
 //          -> join streams -> hm_fold_kernel (stream bests -> 16-B result)
 //   multi-device: contiguous shards, then either a host merge of the 16-B
 //          results or an RCCL all-gather of them (HM_OPT_MERGE_RCCL).
+//   hm_find (ABI 1.10): find_locked below, the kernels of find_kernels.hip.
 //   The scan kernels come from their own code object (scan_kernels.hip ->
 //   align_loops.py -> hipminer_scan.hsaco, embedded by scan_blob.S), loaded
 //   per device with hipModuleLoadData and launched with hipModuleLaunchKernel.
@@ -121,6 +122,7 @@ struct Device {
     uint64_t* best = nullptr;      // [kMaxBatch][kStreams][2]: per request, per stream
     uint64_t* result = nullptr;    // [kMaxBatch][2]
     uint64_t* gathered = nullptr;  // [ndev][kMaxBatch][2] (RCCL merge)
+    uint64_t* find_ctl = nullptr;  // hm_find: [0] the stop word, [1] tasks run (kernels.hpp FindArgs)
     hm_result* host_out = nullptr; // pinned, fine-grained [kMaxBatch]: the 16-B readback slots
     hipEvent_t join[kStreams] = {};
     hipEvent_t gate = nullptr;     // stream 0 reached its last dominant segment
@@ -187,6 +189,8 @@ struct hm_ctx {
     bool have_stats = false;
     int merge = HM_MERGE_NONE;  // how the current call merged device results
     hm_stats last{};
+    bool have_find_stats = false;  // hm_find keeps its own record: `last` stays the last scan's
+    hm_find_stats last_find{};
 };
 
 namespace {
@@ -239,6 +243,7 @@ int device_init(Device& dv, int ordinal) {
     HIPCHK(hipMalloc(&dv.best, (size_t)kMaxBatch * kStreams * 2 * sizeof(uint64_t)));
     HIPCHK(hipMalloc(&dv.acc, (size_t)kStreams * 2 * sizeof(uint64_t)));
     HIPCHK(hipMalloc(&dv.result, (size_t)kMaxBatch * 2 * sizeof(uint64_t)));
+    HIPCHK(hipMalloc(&dv.find_ctl, 2 * sizeof(uint64_t)));
     // pinned readback slots of the 16-B result copies
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&dv.host_out), kMaxBatch * sizeof(hm_result),
                          hipHostMallocMapped | hipHostMallocCoherent));
@@ -273,6 +278,7 @@ void device_free(Device& dv) {
     if (dv.acc) (void)hipFree(dv.acc);
     if (dv.result) (void)hipFree(dv.result);
     if (dv.gathered) (void)hipFree(dv.gathered);
+    if (dv.find_ctl) (void)hipFree(dv.find_ctl);
     if (dv.host_out) (void)hipHostFree(dv.host_out);
     dv.ordinal = -1;
 }
@@ -484,12 +490,16 @@ int kw_table_rows(hm_ctx* ctx, Device& dv, int si, uint64_t rows) {
     return HM_OK;
 }
 
-// One chained launch: tiles [t, t + nt) of segment s in epoch e (final-block
-// values e * nloop + [0, nloop), K+W table already built on stream si).
-int launch_chained_tiles(hm_ctx* ctx, Device& dv, const MsgPlan& mp, const SegPlan& s, int si,
-                         uint64_t* best, uint64_t t, uint64_t nt, uint64_t e, uint64_t nep) {
-    hipStream_t st = dv.stream[si];
-    const uint64_t nloop = pow10_u64(s.fe);
+// ---------------------------------------------------------------------------
+// Argument blocks of the per-segment launches, filled from a SegPlan.  The
+// scan path (enqueue_segment, launch_chained_tiles) and the find path
+// (find_issue) both fill theirs here, so a layout or argument change is made
+// once.  The output fields (cand, sums) are left null: only the scan sets them.
+// ---------------------------------------------------------------------------
+// The tile planner's arguments for tiles [t, t + nt) of s on stream si.  The
+// chained layout keeps tail block 0 raw (fb = 0): its compression is per lane.
+PlanArgs plan_args(const Device& dv, const MsgPlan& mp, const SegPlan& s, int si, uint64_t t,
+                   uint64_t nt) {
     PlanArgs pa;
     pa.rec = dv.rec[si];
     pa.tile0 = t;
@@ -499,17 +509,49 @@ int launch_chained_tiles(hm_ctx* ctx, Device& dv, const MsgPlan& mp, const SegPl
     pa.V = s.V;
     pa.d = s.d;
     pa.r = mp.r;
-    pa.fb = 0;  // keep tail block 0 raw; its compression is per lane
+    pa.fb = s.kind == HM_KIND_CHAINED ? 0 : s.fb;
     pa.nb = s.nb;
     memcpy(pa.pw, mp.pw, sizeof pa.pw);
     memcpy(pa.mid, mp.mid, sizeof pa.mid);
-    HIPCHK(launch_tile_plan(pa, st));
-    ChainedArgs ca;
+    return pa;
+}
+
+// A tiled launch over tiles [t, t + nt) of s, but for its task list
+// (queue_tasks); kw = the trailer block's K+W (zeros without a trailer).
+// *unit0, *nunits: the units kept (launch_units).
+void tiled_args(const hm_ctx* ctx, const Device& dv, const SegPlan& s, int si, uint64_t t,
+                uint64_t nt, const uint32_t kw[64], TiledArgs& ta, uint32_t* unit0,
+                uint64_t* nunits) {
+    ta.rec = dv.rec[si];
+    ta.counter = dv.counter[si];
+    ta.cand = nullptr;
+    ta.sums = nullptr;
+    ta.tile0 = t;
+    ta.pow10V = s.pow10V;
+    ta.seg_lo = s.lo;
+    ta.seg_hi = s.hi;
+    launch_units(s, t, nt, 1, 100, unit0, nunits);
+    ta.tpt = s.tpt;
+    ta.vmax = (uint32_t)(pow10_u64(s.q) - 1);
+    ta.q = s.q;
+    ta.lane_shift = s.lane_shift;
+    ta.loop_shift = s.loop_shift;
+    ta.lds_shift = queue_shift(ctx, tile_span_nonces(s, t, nt));
+    memcpy(ta.trailer_kw, kw, sizeof ta.trailer_kw);
+    tiled_loop_sigma0(s, ta.s0_loop);
+}
+
+// A chained launch over tiles [t, t + nt) of s in epoch e of nep, but for
+// its task list.
+void chained_args(const hm_ctx* ctx, const Device& dv, const SegPlan& s, int si, uint64_t t,
+                  uint64_t nt, uint64_t e, uint64_t nep, ChainedArgs& ca, uint32_t* unit0,
+                  uint64_t* nunits) {
+    const uint64_t nloop = pow10_u64(s.fe);
     ca.rec = dv.rec[si];
     ca.kwt = dv.kwt[si];
     ca.counter = dv.counter[si];
-    ca.cand = dv.cand[si];
-    ca.sums = ctx->csum ? dv.sums[si] : nullptr;
+    ca.cand = nullptr;
+    ca.sums = nullptr;
     ca.tile0 = t;
     ca.pow10qf = s.pow10V;
     ca.pow10f = pow10_u64(s.f);
@@ -517,27 +559,91 @@ int launch_chained_tiles(hm_ctx* ctx, Device& dv, const MsgPlan& mp, const SegPl
     ca.nloop = (uint32_t)nloop;
     ca.seg_lo = s.lo;
     ca.seg_hi = s.hi;
-    uint32_t unit0;
-    uint64_t nunits;
-    launch_units(s, t, nt, s.ntc, pow10_u64(s.f), &unit0, &nunits);
+    launch_units(s, t, nt, s.ntc, pow10_u64(s.f), unit0, nunits);
     ca.tpt = s.tpt;
     ca.ntc = s.ntc;
     ca.tch = s.tch;
     ca.vmax = (uint32_t)(pow10_u64(s.q) - 1);
     ca.q = s.q;
     ca.lds_shift = queue_shift(ctx, tile_span_nonces(s, t, nt) / nep);
+}
+
+// A generic launch over the count_m1 + 1 nonces from lo of segment s.
+void generic_args(const MsgPlan& mp, const SegPlan& s, uint64_t lo, uint64_t count_m1,
+                  GenericArgs& ga) {
+    ga.cand = nullptr;
+    ga.sums = nullptr;
+    ga.seg_lo = lo;
+    ga.count_m1 = count_m1;
+    ga.total_bits = s.total_bits;
+    ga.d = s.d;
+    ga.r = mp.r;
+    ga.nb = s.nb;
+    memcpy(ga.pw, mp.pw, sizeof ga.pw);
+    memcpy(ga.mid, mp.mid, sizeof ga.mid);
+}
+int generic_grid(const Device& dv, uint64_t count_m1) {
+    const uint64_t need = count_m1 / kBlock + 1;
+    const uint64_t cap = (uint64_t)(kMaxCandWaves / (kBlock / kWaveSize));
+    return (int)std::min<uint64_t>(need, std::min<uint64_t>(cap, (uint64_t)dv.cus * 8));
+}
+
+// Grid and guided task list of a persistent launch of fn over nunits units
+// from unit0, and the queue counter's reset on stream si.  Task ids start at
+// unit0 (the queue counter too): the kernels map a task below nbig to that
+// unit, so the skipped units are never dequeued.  *ntasks, *nbig: the
+// launch's argument fields (unit0 included); *count: the tasks themselves.
+int queue_tasks(const hm_ctx* ctx, const Device& dv, const Device::Fn& fn, int si,
+                uint64_t nunits, uint32_t unit0, uint32_t* ntasks, uint32_t* nbig,
+                uint32_t* count, int* grid) {
+    *grid = plan_launch(ctx, dv, fn.blocks_per_cu, nunits, ntasks, nbig);
+    *count = *ntasks;
+    *ntasks += unit0;
+    *nbig += unit0;
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)dv.counter[si], (int)unit0, 1, dv.stream[si]));
+    return HM_OK;
+}
+
+// Make stream si's K+W table hold segment s's 10^fe rows.  A device short of
+// memory for the planned table gets smaller tables and more epochs: the same
+// nonces on the same kernel, more launches (s.fe, s.tch, s.ntc shrink).
+int chained_table(hm_ctx* ctx, Device& dv, int si, SegPlan& s) {
+    if (s.fe < 1 || s.fe > kMaxTableDigits || s.fe > s.f) return HM_ERR_INTERNAL;
+    int rc;
+    while ((rc = kw_table_rows(ctx, dv, si, pow10_u64(s.fe))) == HM_ERR_NOMEM && s.fe > 1) {
+        --s.fe;
+        s.tch = (uint32_t)std::min<uint64_t>(s.tch, pow10_u64(s.fe));
+        s.ntc = (uint32_t)(pow10_u64(s.fe) / s.tch);
+    }
+    return rc;
+}
+// Tiles one launch of s may cover.
+uint64_t max_launch_tiles(const SegPlan& s) {
+    const uint64_t per_tile = s.kind == HM_KIND_CHAINED ? (uint64_t)s.tpt * s.ntc : s.tpt;
+    return std::min<uint64_t>(kMaxTilesPerLaunch, 0x7fffffffull / per_tile);
+}
+
+// One chained launch: tiles [t, t + nt) of segment s in epoch e (final-block
+// values e * nloop + [0, nloop), K+W table already built on stream si).
+int launch_chained_tiles(hm_ctx* ctx, Device& dv, const MsgPlan& mp, const SegPlan& s, int si,
+                         uint64_t* best, uint64_t t, uint64_t nt, uint64_t e, uint64_t nep) {
+    hipStream_t st = dv.stream[si];
+    HIPCHK(launch_tile_plan(plan_args(dv, mp, s, si, t, nt), st));
+    ChainedArgs ca;
+    uint32_t unit0, ntasks;
+    uint64_t nunits;
+    chained_args(ctx, dv, s, si, t, nt, e, nep, ca, &unit0, &nunits);
+    ca.cand = dv.cand[si];
+    ca.sums = ctx->csum ? dv.sums[si] : nullptr;
     const Device::Fn* fn = nullptr;
     int rc = scan_fn(dv, chained_symbol(ctx->csum), &fn);
     if (rc) return rc;
-    const int grid = plan_launch(ctx, dv, fn->blocks_per_cu, nunits, &ca.ntasks, &ca.nbig);
+    int grid;
+    rc = queue_tasks(ctx, dv, *fn, si, nunits, unit0, &ca.ntasks, &ca.nbig, &ntasks, &grid);
+    if (rc) return rc;
     // every task compresses its lanes' tail block 0 once; the final block
     // runs once per lane and loop value: nunits * tch values per lane
-    const double block0_per_value = (double)ca.ntasks / ((double)nunits * (double)s.tch);
-    // task ids start at unit0 (the queue counter too): the kernels map a
-    // task below nbig to that unit, so the skipped units are never dequeued
-    ca.ntasks += unit0;
-    ca.nbig += unit0;
-    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)dv.counter[si], (int)unit0, 1, st));
+    const double block0_per_value = (double)ntasks / ((double)nunits * (double)s.tch);
     Launch L;
     rc = next_event(dv, &L.start);
     if (rc) return rc;
@@ -565,21 +671,12 @@ int launch_chained_tiles(hm_ctx* ctx, Device& dv, const MsgPlan& mp, const SegPl
 
 int enqueue_chained(hm_ctx* ctx, Device& dv, const MsgPlan& mp, const SegPlan& plan, int si,
                     uint64_t* best) {
-    if (plan.fe < 1 || plan.fe > kMaxTableDigits || plan.fe > plan.f) return HM_ERR_INTERNAL;
-    // a device short of memory for the planned table gets smaller tables and
-    // more epochs: the same nonces on the same kernel, more launches
     SegPlan s = plan;
-    int rc;
-    while ((rc = kw_table_rows(ctx, dv, si, pow10_u64(s.fe))) == HM_ERR_NOMEM && s.fe > 1) {
-        --s.fe;
-        s.tch = (uint32_t)std::min<uint64_t>(s.tch, pow10_u64(s.fe));
-        s.ntc = (uint32_t)(pow10_u64(s.fe) / s.tch);
-    }
+    int rc = chained_table(ctx, dv, si, s);
     if (rc) return rc;
     const uint64_t nloop = pow10_u64(s.fe);       // table rows = loop values per lane
     const uint64_t nep = pow10_u64(s.f - s.fe);   // epochs: the final block's high digits
-    const uint64_t per_tile = (uint64_t)s.tpt * s.ntc;
-    const uint64_t max_tiles = std::min<uint64_t>(kMaxTilesPerLaunch, 0x7fffffffull / per_tile);
+    const uint64_t max_tiles = max_launch_tiles(s);
     for (uint64_t e = 0; e < nep; ++e) {
         HIPCHK(launch_kw_table(dv.kwt[si], s.f, s.fe, e * nloop, s.total_bits, dv.stream[si]));
         for (uint64_t t = s.tile_lo; t <= s.tile_hi;) {
@@ -602,51 +699,22 @@ int enqueue_segment(hm_ctx* ctx, Device& dv, const MsgPlan& mp, const SegPlan& s
     if (s.kind == HM_KIND_TILED) {
         uint32_t kw[64] = {0};
         if (s.trailer) trailer_kw(s, kw);
-        const uint64_t max_tiles =
-            std::min<uint64_t>(kMaxTilesPerLaunch, (uint64_t)0x7fffffffu / s.tpt);
+        const uint64_t max_tiles = max_launch_tiles(s);
         for (uint64_t t = s.tile_lo; t <= s.tile_hi;) {
             const uint64_t nt = std::min<uint64_t>(max_tiles, s.tile_hi - t + 1);
-            PlanArgs pa;
-            pa.rec = dv.rec[si];
-            pa.tile0 = t;
-            pa.pow10V = s.pow10V;
-            pa.total_bits = s.total_bits;
-            pa.ntiles = (uint32_t)nt;
-            pa.V = s.V;
-            pa.d = s.d;
-            pa.r = mp.r;
-            pa.fb = s.fb;
-            pa.nb = s.nb;
-            memcpy(pa.pw, mp.pw, sizeof pa.pw);
-            memcpy(pa.mid, mp.mid, sizeof pa.mid);
-            HIPCHK(launch_tile_plan(pa, st));
+            HIPCHK(launch_tile_plan(plan_args(dv, mp, s, si, t, nt), st));
             TiledArgs ta;
-            ta.rec = dv.rec[si];
-            ta.counter = dv.counter[si];
+            uint32_t unit0, ntasks;
+            uint64_t nunits;
+            tiled_args(ctx, dv, s, si, t, nt, kw, ta, &unit0, &nunits);
             ta.cand = dv.cand[si];
             ta.sums = ctx->csum ? dv.sums[si] : nullptr;
-            ta.tile0 = t;
-            ta.pow10V = s.pow10V;
-            ta.seg_lo = s.lo;
-            ta.seg_hi = s.hi;
-            uint32_t unit0;
-            uint64_t nunits;
-            launch_units(s, t, nt, 1, 100, &unit0, &nunits);
-            ta.tpt = s.tpt;
-            ta.vmax = (uint32_t)(pow10_u64(s.q) - 1);
-            ta.q = s.q;
-            ta.lane_shift = s.lane_shift;
-            ta.loop_shift = s.loop_shift;
-            ta.lds_shift = queue_shift(ctx, tile_span_nonces(s, t, nt));
-            memcpy(ta.trailer_kw, kw, sizeof kw);
-            tiled_loop_sigma0(s, ta.s0_loop);
             const Device::Fn* fn = nullptr;
             int rc = scan_fn(dv, tiled_symbol(s, ctx->csum), &fn);
             if (rc) return rc;
-            const int grid = plan_launch(ctx, dv, fn->blocks_per_cu, nunits, &ta.ntasks, &ta.nbig);
-            ta.ntasks += unit0;  // see enqueue_chained
-            ta.nbig += unit0;
-            HIPCHK(hipMemsetD32Async((hipDeviceptr_t)dv.counter[si], (int)unit0, 1, st));
+            int grid;
+            rc = queue_tasks(ctx, dv, *fn, si, nunits, unit0, &ta.ntasks, &ta.nbig, &ntasks, &grid);
+            if (rc) return rc;
             Launch L;
             rc = next_event(dv, &L.start);
             if (rc) return rc;
@@ -675,19 +743,10 @@ int enqueue_segment(hm_ctx* ctx, Device& dv, const MsgPlan& mp, const SegPlan& s
     }
     // generic
     GenericArgs ga;
+    generic_args(mp, s, s.lo, s.hi - s.lo, ga);
     ga.cand = dv.cand[si];
     ga.sums = ctx->csum ? dv.sums[si] : nullptr;
-    ga.seg_lo = s.lo;
-    ga.count_m1 = s.hi - s.lo;
-    ga.total_bits = s.total_bits;
-    ga.d = s.d;
-    ga.r = mp.r;
-    ga.nb = s.nb;
-    memcpy(ga.pw, mp.pw, sizeof ga.pw);
-    memcpy(ga.mid, mp.mid, sizeof ga.mid);
-    const uint64_t need = ga.count_m1 / kBlock + 1;
-    const uint64_t cap = (uint64_t)(kMaxCandWaves / (kBlock / kWaveSize));
-    const int grid = (int)std::min<uint64_t>(need, std::min<uint64_t>(cap, (uint64_t)dv.cus * 8));
+    const int grid = generic_grid(dv, ga.count_m1);
     const Device::Fn* fn = nullptr;
     int rc = scan_fn(dv, generic_symbol(ctx->csum), &fn);
     if (rc) return rc;
@@ -1224,7 +1283,8 @@ uint64_t hm_hash(const uint8_t* msg, size_t len, uint64_t nonce) {
 // 1.9: option ids 16 and 18 (rejected experiment hooks) retired:
 //      hm_set_option answers HM_ERR_INVALID; the wave-timeline debug export removed;
 //      test and experiment hooks and hm_debug_* prototypes moved to hipminer_debug.h
-int hm_version(void) { return (1 << 16) | 9; }
+// 1.10: hm_find, hm_find_cpu, hm_find_stats_sized
+int hm_version(void) { return (1 << 16) | 10; }
 
 // The digest of the sources this library was built from (build_id.py), kept
 // in the binary behind a tag so tools can read it without loading the library.
@@ -1522,6 +1582,372 @@ int scan_many_locked(hm_ctx* ctx, const hm_request* reqs, int n, hm_result* outs
     return HM_OK;
 }
 
+// ---------------------------------------------------------------------------
+// hm_find: the lowest nonce of [lo, hi] whose hash is below `target`
+// (find_kernels.hip has the device protocol and its three invariants).
+//
+// Host side.  The range is planned with plan_range; each digit segment is
+// one piece (with several devices: pieces of at most kFindPieceNonces per
+// device, cut at tile boundaries and split across the devices with
+// partition_range).  Pieces are processed in ascending order.  Within a
+// piece every device walks its shard's launches in ascending order on stream
+// 0, at most kFindLookahead in flight: it issues that many, waits for them
+// (host_wait), and reads its stop word and task counter back (host_read).
+// A launch whose smallest nonce is above the lowest hit known so far is
+// never issued, and the call ends once that holds for every launch left: a
+// hit is known, and all work not yet issued lies above it.  A launch
+// already in flight when a hit is published exits on its first read of the
+// word.
+//
+// Chained segments with epochs run epoch by epoch over the same tiles, so
+// their launches are not ascending: launch (e, t) starts at t * 10^V +
+// e * 10^fe.  The rule is applied per launch there -- within an epoch the
+// tiles above the hit are dropped, and the call ends when an epoch's first
+// launch is above it -- and a task's lanes stride 10^f nonces, so a hit
+// prunes only the tasks that start above it: later epochs still run the
+// tasks that start below the hit (their in-range nonces above it are
+// ignored by the wave's bound).  That is the loss of pruning: exactness is
+// unaffected.
+//
+// A hit at nonce MaxUint64 cannot be told from "none" in the stop word, so
+// the kernels never publish it and the host tests that one nonce itself.
+// ---------------------------------------------------------------------------
+constexpr int kFindLookahead = 4;
+constexpr uint64_t kFindPieceNonces = 1ull << 40;   // per device and piece (multi-device)
+constexpr uint64_t kFindGenericNonces = 1ull << 30; // per generic launch
+
+const char* find_chained_symbol() { return "_ZN2hm22hm_find_chained_kernelENS_15FindChainedArgsE"; }
+const char* find_generic_symbol() { return "_ZN2hm22hm_find_generic_kernelENS_15FindGenericArgsE"; }
+std::string find_tiled_symbol(const SegPlan& s) {
+    char b[128];
+    snprintf(b, sizeof b, "_ZN2hm20hm_find_tiled_kernelILi%dELb%dELb%dEEEvNS_13FindTiledArgsE", s.W1,
+             s.straddle ? 1 : 0, s.trailer ? 1 : 0);
+    return b;
+}
+
+// One device's walk through its shard of a piece.
+struct FindDev {
+    std::vector<SegPlan> segs;  // the shard's segments (one digit count: one)
+    size_t si = 0;
+    bool seg_open = false;      // cursor below is set for segs[si]
+    uint64_t t = 0, e = 0, nep = 1, max_tiles = 0;  // tiled / chained
+    uint64_t table_epoch = ~0ull;                   // chained: epoch of the K+W table on the stream
+    uint64_t g = 0;                                 // generic: next nonce
+    bool g_done = false;
+    int inflight = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
+    uint64_t word = ~0ull, run = 0;  // last readback
+};
+
+struct FindTally {
+    uint64_t nonces = 0, tasks = 0;
+    int launches = 0;
+    double kernel_ms = 0;
+};
+
+int find_events(Device& dv, FindDev& fd, hipStream_t st, bool stop) {
+    if (!stop) {
+        hipEvent_t a, b;
+        int rc = next_event(dv, &a);
+        if (rc) return rc;
+        rc = next_event(dv, &b);
+        if (rc) return rc;
+        fd.evs.push_back({a, b});
+        HIPCHK(hipEventRecord(a, st));
+    } else {
+        HIPCHK(hipEventRecord(fd.evs.back().second, st));
+    }
+    return HM_OK;
+}
+
+FindArgs find_args(const Device& dv, uint64_t target, uint64_t launch_lo) {
+    FindArgs f;
+    f.word = dv.find_ctl;
+    f.tasks_run = dv.find_ctl + 1;
+    f.target = target;
+    f.launch_lo = launch_lo;
+    return f;
+}
+
+// Prepare segs[si] for launching (chained: its table, chained_table).
+int find_open_seg(hm_ctx* ctx, Device& dv, FindDev& fd) {
+    SegPlan& s = fd.segs[fd.si];
+    fd.e = 0;
+    fd.nep = 1;
+    fd.table_epoch = ~0ull;
+    fd.t = s.tile_lo;
+    fd.g = s.lo;
+    fd.g_done = false;
+    if (s.kind == HM_KIND_CHAINED) {
+        int rc = chained_table(ctx, dv, 0, s);
+        if (rc) return rc;
+        fd.nep = pow10_u64(s.f - s.fe);
+    }
+    if (s.kind != HM_KIND_GENERIC) fd.max_tiles = max_launch_tiles(s);
+    fd.seg_open = true;
+    return HM_OK;
+}
+
+// Launch find kernel fn with its argument block between the launch's two
+// timing events, and count the launch.
+template <typename Args>
+int find_launch(Device& dv, FindDev& fd, const Device::Fn& fn, const Args& a, int grid,
+                uint64_t nonces, uint64_t tasks, FindTally& tally) {
+    hipStream_t st = dv.stream[0];
+    int rc = find_events(dv, fd, st, false);
+    if (rc) return rc;
+    rc = launch_scan(fn, a, grid, st);
+    if (rc) return rc;
+    rc = find_events(dv, fd, st, true);
+    if (rc) return rc;
+    tally.nonces += nonces;
+    tally.tasks += tasks;
+    ++tally.launches;
+    ++fd.inflight;
+    return HM_OK;
+}
+
+// Issue the device's next launch whose smallest nonce is <= best (the lowest
+// hit known; MaxUint64 = none).  *issued = false: nothing left to issue in
+// this piece.  The argument blocks are the scan path's (plan_args,
+// tiled_args, chained_args, generic_args, queue_tasks) plus FindArgs.
+int find_issue(hm_ctx* ctx, Device& dv, FindDev& fd, const MsgPlan& mp, uint64_t target,
+               uint64_t best, FindTally& tally, bool* issued) {
+    *issued = false;
+    hipStream_t st = dv.stream[0];
+    for (;;) {
+        if (fd.si >= fd.segs.size()) return HM_OK;
+        if (!fd.seg_open) {
+            int rc = find_open_seg(ctx, dv, fd);
+            if (rc) return rc;
+        }
+        const SegPlan& s = fd.segs[fd.si];
+        if (s.lo > best) {  // this segment and every later one lie above the hit
+            fd.si = fd.segs.size();
+            return HM_OK;
+        }
+        const Device::Fn* fn = nullptr;
+        int rc;
+        if (s.kind == HM_KIND_GENERIC) {
+            if (fd.g_done || fd.g > best) { ++fd.si; fd.seg_open = false; continue; }
+            FindGenericArgs a;
+            generic_args(mp, s, fd.g, std::min<uint64_t>(s.hi - fd.g, kFindGenericNonces - 1), a.g);
+            a.f = find_args(dv, target, fd.g);
+            const uint64_t count_m1 = a.g.count_m1;
+            rc = scan_fn(dv, find_generic_symbol(), &fn);
+            if (rc) return rc;
+            // a task: one wave step of 64 nonces
+            rc = find_launch(dv, fd, *fn, a, generic_grid(dv, count_m1), count_m1 + 1,
+                             count_m1 / kWaveSize + 1, tally);
+            if (rc) return rc;
+            if (s.hi - fd.g == count_m1) fd.g_done = true;
+            else fd.g += count_m1 + 1;
+            *issued = true;
+            return HM_OK;
+        }
+        const bool ch = s.kind == HM_KIND_CHAINED;
+        const uint64_t nloop = ch ? pow10_u64(s.fe) : 0;
+        if (fd.e >= fd.nep) { ++fd.si; fd.seg_open = false; continue; }
+        // the launch's smallest nonce (a wrap past 2^64 in a segment's last
+        // tile only makes it look lower: a launch more, never one less)
+        const bool past = fd.t > s.tile_hi;
+        const uint64_t base = past ? 0 : fd.t * s.pow10V + fd.e * nloop;
+        if (past || base > best) {
+            // the rest of this epoch is done or above the hit; when its
+            // first launch already is, so is every later epoch
+            if (!past && fd.t == s.tile_lo) { ++fd.si; fd.seg_open = false; continue; }
+            ++fd.e;
+            fd.t = s.tile_lo;
+            continue;
+        }
+        const uint64_t t = fd.t;
+        const uint64_t nt = std::min<uint64_t>(fd.max_tiles, s.tile_hi - t + 1);
+        const uint64_t span = tile_span_nonces(s, t, nt);
+        const FindArgs fa = find_args(dv, target, std::max(s.lo, base));
+        uint32_t unit0, ntasks;
+        uint64_t nunits;
+        int grid;
+        if (ch && fd.table_epoch != fd.e) {
+            HIPCHK(launch_kw_table(dv.kwt[0], s.f, s.fe, fd.e * nloop, s.total_bits, st));
+            fd.table_epoch = fd.e;
+        }
+        HIPCHK(launch_tile_plan(plan_args(dv, mp, s, 0, t, nt), st));
+        if (ch) {
+            FindChainedArgs a;
+            chained_args(ctx, dv, s, 0, t, nt, fd.e, fd.nep, a.c, &unit0, &nunits);
+            a.f = fa;
+            rc = scan_fn(dv, find_chained_symbol(), &fn);
+            if (rc) return rc;
+            rc = queue_tasks(ctx, dv, *fn, 0, nunits, unit0, &a.c.ntasks, &a.c.nbig, &ntasks, &grid);
+            if (rc) return rc;
+            // the epochs split every lane value's nonces evenly: the launch's
+            // share of the span, as the scan's stats count it (an estimate)
+            rc = find_launch(dv, fd, *fn, a, grid,
+                             span / fd.nep + (fd.e + 1 == fd.nep ? span % fd.nep : 0), ntasks, tally);
+        } else {
+            FindTiledArgs a;
+            uint32_t kw[64] = {0};
+            if (s.trailer) trailer_kw(s, kw);
+            tiled_args(ctx, dv, s, 0, t, nt, kw, a.t, &unit0, &nunits);
+            a.f = fa;
+            rc = scan_fn(dv, find_tiled_symbol(s), &fn);
+            if (rc) return rc;
+            rc = queue_tasks(ctx, dv, *fn, 0, nunits, unit0, &a.t.ntasks, &a.t.nbig, &ntasks, &grid);
+            if (rc) return rc;
+            rc = find_launch(dv, fd, *fn, a, grid, span, ntasks, tally);
+        }
+        if (rc) return rc;
+        fd.t = t + nt;
+        if (fd.t == 0) fd.t = s.tile_hi + 1;  // tile index wrapped (cannot happen for d <= 20)
+        *issued = true;
+        return HM_OK;
+    }
+}
+
+// Wait for the device's launches in flight and read its stop word and task
+// counter back.
+int find_collect(hm_ctx* ctx, Device& dv, FindDev& fd, FindTally& tally) {
+    HIPCHK(hipSetDevice(dv.ordinal));
+    int rc = host_wait(ctx, dv.stream[0]);
+    if (rc) return rc;
+    uint64_t ctl[2];
+    rc = host_read(ctx, ctl, dv.find_ctl, sizeof ctl);
+    if (rc) return rc;
+    fd.word = ctl[0];
+    fd.run = ctl[1];
+    for (const auto& ev : fd.evs) {
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, ev.first, ev.second));
+        tally.kernel_ms += ms;
+    }
+    fd.evs.clear();
+    dv.evnext = 0;  // the events are free again
+    fd.inflight = 0;
+    return HM_OK;
+}
+
+// A find that fails part-way leaves nothing behind: every device's stream 0
+// is waited for (launches still queued use its record, table, counter and
+// control buffers) and its timing events are free again.  After a timeout
+// the context is abandoned and nothing is waited for, as for a scan.
+int find_fail(hm_ctx* ctx, std::vector<FindDev>& fds, int rc) {
+    if (rc == HM_ERR_TIMEOUT || ctx->abandoned) return rc;
+    for (size_t i = 0; i < fds.size(); ++i) {
+        Device& dv = ctx->devs[i];
+        if (hipSetDevice(dv.ordinal) == hipSuccess && host_wait(ctx, dv.stream[0]) != HM_OK) break;
+        fds[i].evs.clear();
+        fds[i].inflight = 0;
+        dv.evnext = 0;
+    }
+    return rc;
+}
+
+// hm_find with ctx->mu held.
+int find_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
+                uint64_t target, hm_result* out, int* found) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (ctx->abandoned) return HM_ERR_TIMEOUT;
+    static const uint8_t empty_msg = 0;
+    const uint8_t* m = msg ? msg : &empty_msg;
+    const size_t mlen = msg ? len : 0;
+    const hm_request whole{m, mlen, lo, hi};
+    ctx->has_deadline = ctx->deadline_opt != 0;
+    ctx->deadline_ms = !ctx->has_deadline ? 0.0
+                       : ctx->deadline_opt > 0 ? (double)ctx->deadline_opt
+                                               : auto_deadline_ms(ctx, &whole, 1);
+    if (ctx->has_deadline)
+        ctx->deadline_at = t0 + std::chrono::duration_cast<std::chrono::steady_clock::duration>(
+                                    std::chrono::duration<double, std::milli>(ctx->deadline_ms));
+    const int ndev = (int)ctx->devs.size();
+    FindTally tally;
+    uint64_t best = ~0ull, run = 0;
+    if (lo <= hi && target != 0) {
+        const MsgPlan mp = plan_message(m, mlen);
+        for (auto& dv : ctx->devs) {
+            HIPCHK(hipSetDevice(dv.ordinal));
+            dv.evnext = 0;
+            // the stop word starts at MaxUint64, the task counter at 0
+            HIPCHK(hipMemsetAsync(dv.find_ctl, 0xff, sizeof(uint64_t), dv.stream[0]));
+            HIPCHK(hipMemsetAsync(dv.find_ctl + 1, 0, sizeof(uint64_t), dv.stream[0]));
+        }
+        std::vector<FindDev> fds(ndev);
+        for (const SegPlan& seg : plan_range(mp, lo, hi, ctx->force_generic, ctx->table_digits)) {
+            uint64_t span = ~0ull;  // one device: the segment is one piece
+            if (ndev > 1) {
+                span = kFindPieceNonces * (uint64_t)ndev;
+                if (seg.pow10V > 1) span = std::max<uint64_t>(span / seg.pow10V, 1) * seg.pow10V;
+            }
+            for (uint64_t a = seg.lo;;) {
+                // pieces end at multiples of span (tile boundaries)
+                const uint64_t k = a / span;
+                const uint64_t b =
+                    ndev == 1 || k >= ~0ull / span ? seg.hi : std::min(seg.hi, (k + 1) * span - 1);
+                const std::vector<Shard> sh = partition_range(mp, a, b, ndev, ctx->force_generic);
+                for (int i = 0; i < ndev; ++i) {
+                    FindDev& fd = fds[i];
+                    fd.segs.clear();
+                    fd.si = 0;
+                    fd.seg_open = false;
+                    if (!sh[i].empty)
+                        fd.segs = plan_range(mp, sh[i].lo, sh[i].hi, ctx->force_generic,
+                                             ctx->table_digits);
+                }
+                for (;;) {
+                    bool any = false;
+                    for (int i = 0; i < ndev; ++i) {
+                        Device& dv = ctx->devs[i];
+                        HIPCHK(hipSetDevice(dv.ordinal));
+                        while (fds[i].inflight < kFindLookahead) {
+                            bool issued = false;
+                            int rc = find_issue(ctx, dv, fds[i], mp, target, best, tally, &issued);
+                            if (rc) return find_fail(ctx, fds, rc);
+                            if (!issued) break;
+                        }
+                        any = any || fds[i].inflight > 0;
+                    }
+                    if (!any) break;
+                    for (int i = 0; i < ndev; ++i) {
+                        if (!fds[i].inflight) continue;
+                        int rc = find_collect(ctx, ctx->devs[i], fds[i], tally);
+                        if (rc) return find_fail(ctx, fds, rc);
+                        best = std::min(best, fds[i].word);
+                    }
+                }
+                if (best != ~0ull || b == seg.hi) break;  // later pieces lie above a hit
+                a = b + 1;
+            }
+            if (best != ~0ull) break;
+        }
+        for (const FindDev& fd : fds) run += fd.run;
+    }
+    hm_result res{~0ull, 0};
+    int hit = 0;
+    if (lo <= hi && target != 0) {
+        // nonce MaxUint64 is the one the stop word cannot carry: tested here
+        if (best != ~0ull || (hi == ~0ull && host_hash(m, mlen, ~0ull) < target)) {
+            res.nonce = best;
+            res.hash = host_hash(m, mlen, best);
+            if (res.hash >= target || best < lo || best > hi) return HM_ERR_INTERNAL;
+            hit = 1;
+        }
+    }
+    hm_find_stats st{};
+    st.kernel_ms = tally.kernel_ms;
+    st.nonces_enqueued = tally.nonces;
+    st.tasks_total = tally.tasks;
+    st.tasks_run = run;
+    st.launches = tally.launches;
+    st.ndev = ndev;
+    st.found = hit;
+    st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
+                     .count();
+    ctx->last_find = st;
+    ctx->have_find_stats = true;
+    *out = res;
+    *found = hit;
+    return HM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1565,6 +1991,27 @@ int hm_scan_checked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, ui
     return HM_OK;
 }
 
+
+int hm_find(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, uint64_t target,
+            hm_result* out, int* found) {
+    if (!ctx || !out || !found || (!msg && len)) return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    hm_result res;
+    int hit = 0;
+    int rc = guarded([&] { return find_locked(ctx, msg, len, lo, hi, target, &res, &hit); });
+    if (rc) return rc;
+    *out = res;
+    *found = hit;
+    return HM_OK;
+}
+
+int hm_find_stats_sized(const hm_ctx* ctx, hm_find_stats* out, size_t size) {
+    if (!ctx || !out || size < HM_FIND_STATS_SIZE_1_10) return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!ctx->have_find_stats) return HM_ERR_INVALID;
+    memcpy(out, &ctx->last_find, std::min(size, sizeof(hm_find_stats)));
+    return HM_OK;
+}
 
 int hm_scan_stats(const hm_ctx* ctx, hm_stats* out) {
     // frozen at the 1.4/1.5 size (include/hipminer.h): newer fields only

@@ -1,4 +1,5 @@
-// host_scan.cpp -- hm_scan_cpu: the min-hash scan on the host's cores.
+// host_scan.cpp -- hm_scan_cpu and hm_find_cpu: the min-hash scan, and the
+// first-below-target search (ABI 1.10), on the host's cores.
 //
 // SURVEY §8(b)'s liveness path.  The reference miner always answers a
 // Request with a Result (cmu440/bitcoin/miner/miner.go:60-62); a GPU miner
@@ -21,6 +22,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <thread>
 #include <vector>
 
@@ -117,9 +119,10 @@ CompressFn pick_compress() {
     return compress_c;
 }
 
-// Scan [a, b] (a <= b, one thread): every digit segment of it in turn.
-void scan_chunk(const MsgPlan& mp, uint64_t a, uint64_t b, CompressFn compress, Best* out) {
-    Best best;
+// Walk [a, b] (a <= b, one thread) in ascending order, every digit segment of
+// it in turn: visit(key, nonce) per nonce; a true return ends the walk.
+template <typename Visit>
+void walk_chunk(const MsgPlan& mp, uint64_t a, uint64_t b, CompressFn compress, Visit&& visit) {
     const uint32_t r = mp.r;
     for (uint32_t d = digits_u64(a); d <= digits_u64(b); ++d) {
         const uint64_t dlo = d == 1 ? 0 : pow10_u64(d - 1);
@@ -148,7 +151,7 @@ void scan_chunk(const MsgPlan& mp, uint64_t a, uint64_t b, CompressFn compress, 
         for (uint64_t i = 0;; ++i) {
             uint32_t o[8];
             compress(s0, last, o);
-            best.take(((uint64_t)o[0] << 32) | o[1], slo + i);
+            if (visit(((uint64_t)o[0] << 32) | o[1], slo + i)) return;
             if (i == count_m1) break;
             // next nonce: increment the ASCII digits in place (no carry out:
             // every nonce of the segment has d digits)
@@ -158,7 +161,49 @@ void scan_chunk(const MsgPlan& mp, uint64_t a, uint64_t b, CompressFn compress, 
             if (nb == 2 && p < 64) compress(mp.mid, tail, s0);
         }
     }
+}
+
+// Scan [a, b]: the lexicographic minimum of the walk.
+void scan_chunk(const MsgPlan& mp, uint64_t a, uint64_t b, CompressFn compress, Best* out) {
+    Best best;
+    walk_chunk(mp, a, b, compress, [&](uint64_t k, uint64_t n) {
+        best.take(k, n);
+        return false;
+    });
     *out = best;
+}
+
+// hm_find_cpu's shared state.  Threads take ascending windows of kFindWindow
+// nonces from `next`, fold the first hit of a window into `best` (atomic
+// minimum; `hit` tells a hit at nonce MaxUint64 from none) and stop taking
+// windows that start above it.  The three invariants of the GPU protocol
+// (find_kernels.hip) hold here too: only in-range nonces with key < target
+// reach `best`; a window is left out only when all of it lies above a value
+// already in `best`, which only decreases; every window a thread walked has
+// folded its hit before the threads are joined.
+constexpr uint64_t kFindWindow = 1ull << 14;
+struct FindShared {
+    std::atomic<uint64_t> next{0};
+    std::atomic<uint64_t> best{~0ull};
+    std::atomic<bool> hit{false};
+};
+
+void find_worker(const MsgPlan& mp, uint64_t lo, uint64_t hi, uint64_t target, uint64_t nwin,
+                 CompressFn compress, FindShared* sh) {
+    for (;;) {
+        const uint64_t w = sh->next.fetch_add(1, std::memory_order_relaxed);
+        if (w >= nwin) return;
+        const uint64_t a = lo + w * kFindWindow;  // w < nwin: no wrap
+        if (a > sh->best.load(std::memory_order_relaxed)) return;  // so is every later window
+        const uint64_t b = hi - a < kFindWindow - 1 ? hi : a + (kFindWindow - 1);
+        walk_chunk(mp, a, b, compress, [&](uint64_t k, uint64_t n) {
+            if (k >= target) return false;
+            uint64_t cur = sh->best.load(std::memory_order_relaxed);
+            while (n < cur && !sh->best.compare_exchange_weak(cur, n, std::memory_order_relaxed)) {}
+            sh->hit.store(true, std::memory_order_relaxed);
+            return true;  // ascending: the window's first hit is its lowest
+        });
+    }
 }
 
 // Default thread count: the CPUs this process may run on.  A GPU box's
@@ -219,6 +264,53 @@ extern "C" int hm_scan_cpu(const uint8_t* msg, size_t len, uint64_t lo, uint64_t
         Best best;
         for (const Best& p : part) best.take(p.key, p.nonce);
         *out = hm_result{best.key, best.nonce};
+        return HM_OK;
+    } catch (const std::bad_alloc&) {
+        return HM_ERR_NOMEM;
+    } catch (...) {
+        return HM_ERR_INTERNAL;
+    }
+}
+
+extern "C" int hm_find_cpu(const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
+                           uint64_t target, int threads, hm_result* out, int* found) {
+    using namespace hm;
+    if (!out || !found || (!msg && len)) return HM_ERR_INVALID;
+    try {
+        if (lo > hi || target == 0) {
+            *out = hm_result{~0ull, 0};
+            *found = 0;
+            return HM_OK;
+        }
+        static const uint8_t empty = 0;
+        const uint8_t* m = msg ? msg : &empty;
+        const uint64_t mlen = msg ? len : 0;
+        const MsgPlan mp = plan_message(m, mlen);
+        const CompressFn compress = pick_compress();
+        // windows of [lo, hi]: (hi - lo) / kFindWindow + 1 <= 2^50
+        const uint64_t nwin = (hi - lo) / kFindWindow + 1;
+        unsigned n = threads > 0 ? (unsigned)threads : default_threads();
+        n = (unsigned)std::min<uint64_t>(std::min(n, 1024u), nwin);
+        FindShared sh;
+        std::vector<std::thread> pool;
+        pool.reserve(n);
+        for (unsigned t = 0; t + 1 < n; ++t) {
+            try {
+                pool.emplace_back(find_worker, std::cref(mp), lo, hi, target, nwin, compress, &sh);
+            } catch (...) {  // no thread: the started ones and the caller do the work
+                break;
+            }
+        }
+        find_worker(mp, lo, hi, target, nwin, compress, &sh);  // the calling thread
+        for (auto& th : pool) th.join();
+        if (sh.hit.load()) {
+            const uint64_t nn = sh.best.load();
+            *out = hm_result{host_hash(m, mlen, nn), nn};
+            *found = 1;
+        } else {
+            *out = hm_result{~0ull, 0};
+            *found = 0;
+        }
         return HM_OK;
     } catch (const std::bad_alloc&) {
         return HM_ERR_NOMEM;

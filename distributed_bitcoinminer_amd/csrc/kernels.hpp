@@ -211,6 +211,33 @@ struct FusedPlanArgs {
     FusedPlanSeg segs[kMaxFusedSegs];
 };
 
+// ---------------------------------------------------------------------------
+// hm_find (find_kernels.hip, DESIGN.md "First below target"): the lowest
+// nonce whose hash is below a target, with an early exit.  One 64-bit stop
+// word per device holds the lowest qualifying nonce published so far
+// (MaxUint64 = none; it only decreases); a wave reads it before every task and
+// leaves once its next task lies wholly above it.  The find kernels take the
+// scan kernel's argument block (cand and sums unused) plus this one.
+// ---------------------------------------------------------------------------
+struct FindArgs {
+    uint64_t* word;        // the device's stop word
+    uint64_t* tasks_run;   // += tasks whose hash loop ran, once per wave at exit
+    uint64_t target;       // >= 1
+    uint64_t launch_lo;    // the launch's smallest nonce: word < launch_lo -> exit at once
+};
+struct FindTiledArgs {
+    TiledArgs t;
+    FindArgs f;
+};
+struct FindChainedArgs {
+    ChainedArgs c;
+    FindArgs f;
+};
+struct FindGenericArgs {
+    GenericArgs g;
+    FindArgs f;
+};
+
 // Launchers of the auxiliary kernels (kernels.hip; return hipError_t of the
 // launch).  The scan kernels (scan_kernels.hip: hm_tiled_kernel<W1,
 // STRADDLE, TRAILER>, hm_chained_kernel, hm_generic_kernel and their

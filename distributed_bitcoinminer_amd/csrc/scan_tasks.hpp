@@ -51,6 +51,39 @@ DEV void take_step(WaveBest& best, bool cand, uint32_t h0, uint32_t h1, uint64_t
     }
 }
 
+// The per-nonce test of the default (minimum) reduction: may this key beat
+// the wave's best?  One compare against a wave-uniform value.
+DEV bool wave_cand(const WaveBest& best, uint32_t h0) { return h0 <= best.hi; }
+
+// "First below target" reduction (find_kernels.hip, hm_find): the wave keeps
+// the LOWEST nonce n in [seg_lo, seg_hi] with Hash(msg, n) < target instead
+// of the minimum key.  The per-nonce test is h0 <= (target - 1) >> 32, one
+// compare against a wave-uniform constant like the minimum's; only behind the
+// ballot are the 64-bit key, key < target and the range check formed and the
+// wave minimum of the nonce taken.  Nonces at or above `nonce` (the wave's
+// best so far, or a lower hit another wave published) cannot win and are
+// ignored.  nonce = MaxUint64: no hit.
+struct WaveFirst {
+    uint32_t thi;     // (target - 1) >> 32, target >= 1
+    uint64_t target;
+    uint64_t nonce = ~0ull;
+};
+DEV bool wave_cand(const WaveFirst& first, uint32_t h0) { return h0 <= first.thi; }
+DEV void take_step(WaveFirst& first, bool cand, uint32_t h0, uint32_t h1, uint64_t nbase,
+                   uint32_t off, uint64_t seg_lo, uint64_t seg_hi) {
+    if (__builtin_amdgcn_ballot_w64(cand)) {
+        const uint64_t key = ((uint64_t)h0 << 32) | h1;
+        uint64_t nn = nbase + off;
+        const bool ok = cand && key < first.target && nn >= seg_lo && nn <= seg_hi &&
+                        nn < first.nonce;
+        if (!ok) nn = ~0ull;
+        uint64_t zero = 0;  // wave_min orders (nonce, 0) pairs: the minimum nonce
+        wave_min(nn, zero);
+        nn = uni64(nn);
+        if (nn < first.nonce) first.nonce = nn;
+    }
+}
+
 // Workgroup-level task dispenser (round 5; the per-segment kernels and,
 // with kFusedLds, the fused one).  A wave draws a ticket from an
 // LDS counter; the first ticket of each batch of kLdsBatch fetches the
@@ -122,13 +155,16 @@ DEV uint64_t lane_digits(uint32_t v, uint32_t q) {
 // of the loop-digit bits of W[W1] (wave-uniform, read by scalar loads).
 // t0 runs over [t0_begin, t0_end) (the fused launch's split tasks; the
 // per-segment kernels take the constant defaults, so their loop is the full
-// one).
+// one).  Best is the reduction the task folds its nonces into: WaveBest (the
+// running minimum, the default) or WaveFirst (hm_find); each brings its
+// wave_cand (the one compare per nonce) and take_step.
 // ---------------------------------------------------------------------------
-template <int W1, bool STRADDLE, bool TRAILER, bool CSUM, typename S0, typename KW>
+template <int W1, bool STRADDLE, bool TRAILER, bool CSUM, typename S0, typename KW,
+          typename Best = WaveBest>
 DEV void tiled_task(const uint32_t* __restrict__ R, uint32_t chunk, uint32_t t1_begin,
                     uint32_t t1_end, uint64_t tile_base, uint64_t seg_lo, uint64_t seg_hi,
                     uint32_t vmax, uint32_t q, uint32_t lane_shift, uint32_t loop_shift,
-                    S0 s0_loop, KW trailer_kw, WaveBest& best, WaveSums& sums,
+                    S0 s0_loop, KW trailer_kw, Best& best, WaveSums& sums,
                     uint32_t t0_begin = 0, uint32_t t0_end = 10) {
     static_assert(W1 >= 1 && W1 <= 15, "varying words are W[W1-1], W[W1]");
     // Lane digits may reach back into W[W1-2] (the planner does so when the
@@ -221,7 +257,7 @@ DEV void tiled_task(const uint32_t* __restrict__ R, uint32_t chunk, uint32_t t1_
                     ++sums.cnt;
                 }
             }
-            take_step(best, h0 <= best.hi, h0, h1, nbase, t1 * 10u + t0, seg_lo, seg_hi);
+            take_step(best, wave_cand(best, h0), h0, h1, nbase, t1 * 10u + t0, seg_lo, seg_hi);
         }
     }
 }
@@ -233,11 +269,11 @@ DEV void tiled_task(const uint32_t* __restrict__ R, uint32_t chunk, uint32_t t1_
 // block is wave-uniform, its K[i]+W[i] schedule row t comes from kwt (scalar
 // loads).  nbase = the first nonce of the lane value (epoch included).
 // ---------------------------------------------------------------------------
-template <bool CSUM>
+template <bool CSUM, typename Best = WaveBest>
 DEV void chained_task(const uint32_t* __restrict__ R, uint32_t chunk, uint32_t t_begin,
                       uint32_t t_end, uint64_t tile_base, uint64_t pow10f, uint64_t seg_lo,
                       uint64_t seg_hi, uint32_t vmax, uint32_t q, const uint32_t* kwt,
-                      WaveBest& best, WaveSums& sums) {
+                      Best& best, WaveSums& sums) {
     const uint32_t lane = __lane_id();
     uint32_t st[8], W[16];
 #pragma unroll
@@ -274,7 +310,7 @@ DEV void chained_task(const uint32_t* __restrict__ R, uint32_t chunk, uint32_t t
                 ++sums.cnt;
             }
         }
-        take_step(best, h0 <= best.hi, h0, u.b + cs.b, nbase, t, seg_lo, seg_hi);
+        take_step(best, wave_cand(best, h0), h0, u.b + cs.b, nbase, t, seg_lo, seg_hi);
     }
 }
 

@@ -50,6 +50,17 @@ def merge(results) -> tuple[int, int]:
     return best
 
 
+def merge_first(results):
+    """Merge of per-shard find results (``Context.find`` / ``find_cpu``: a
+    ``(hash, nonce)`` pair or None): the hit with the LOWEST nonce, or None.
+    Shards of one range are disjoint, so this is the range's first hit."""
+    best = None
+    for r in results:
+        if r is not None and (best is None or int(r[1]) < best[1]):
+            best = (int(r[0]), int(r[1]))
+    return best
+
+
 def _pack(res) -> np.ndarray:
     return np.array([res[0], res[1]], dtype=np.uint64).view(np.int64)
 

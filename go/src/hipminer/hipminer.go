@@ -184,6 +184,36 @@ func ScanCPU(data string, lo, hi uint64, threads int) (hash, nonce uint64, err e
 	return uint64(out.hash), uint64(out.nonce), nil
 }
 
+// Find is hm_find (ABI 1.10): the LOWEST nonce n of the inclusive range
+// [lo, hi] with Hash(data, n) < target, and its hash; found is false when no
+// nonce qualifies (target 0 and lo > hi never hit).  The call stops as soon
+// as that nonce is known, so [0, MaxUint64] is a valid range.
+func (m *Miner) Find(data string, lo, hi, target uint64) (hash, nonce uint64, found bool, err error) {
+	var out C.hm_result
+	var hit C.int
+	p := cbytes(data)
+	defer C.free(unsafe.Pointer(p))
+	rc := C.hm_find(m.ctx, p, C.size_t(len(data)), C.uint64_t(lo), C.uint64_t(hi), C.uint64_t(target), &out, &hit)
+	if rc != 0 {
+		return 0, 0, false, Error{int(rc)}
+	}
+	return uint64(out.hash), uint64(out.nonce), hit != 0, nil
+}
+
+// FindCPU is hm_find_cpu: Find's answer on the host's cores (threads as for
+// ScanCPU), for a miner whose GPU is missing or failed.
+func FindCPU(data string, lo, hi, target uint64, threads int) (hash, nonce uint64, found bool, err error) {
+	var out C.hm_result
+	var hit C.int
+	p := cbytes(data)
+	defer C.free(unsafe.Pointer(p))
+	rc := C.hm_find_cpu(p, C.size_t(len(data)), C.uint64_t(lo), C.uint64_t(hi), C.uint64_t(target), C.int(threads), &out, &hit)
+	if rc != 0 {
+		return 0, 0, false, Error{int(rc)}
+	}
+	return uint64(out.hash), uint64(out.nonce), hit != 0, nil
+}
+
 // EvalRequestCPU is EvalRequest on the host (ScanCPU), with the same
 // `upper := Upper + 1` wrap and initial (MaxUint64, 0).
 func EvalRequestCPU(data string, lower, upper uint64, threads int) (hash, nonce uint64, err error) {

@@ -15,6 +15,10 @@
  *                      (cmu440/bitcoin/message.go:18-23) and producing the
  *                      values of bitcoin.NewResult(hash, nonce) (:38-44).
  *
+ * hm_find (ABI 1.10) adds the proof-of-work form of that loop, which the
+ * reference does not have: the LOWEST nonce whose hash is below a target,
+ * found without scanning the rest of the range.
+ *
  * The cgo binding a maintainer adds to the Go miner is in INTEGRATION.md.
  *
  * Semantics (bit-exact with the reference):
@@ -288,6 +292,64 @@ int hm_scan_stats_sized(const hm_ctx *ctx, hm_stats *out, size_t size);
  * HM_OK. */
 int hm_scan_cpu(const uint8_t *msg, size_t len, uint64_t lo, uint64_t hi, int threads,
                 hm_result *out);
+
+/* ABI 1.10: the proof-of-work question.  The result of
+ *   for n = lo .. hi (inclusive, ascending): if Hash(msg, n) < target: return (Hash, n)
+ * *found = 1 and *out = (Hash(msg, n), n) for the LOWEST such n; otherwise
+ * *found = 0 and *out = (UINT64_MAX, 0).  target = 0 and lo > hi never hit.
+ * hi may be UINT64_MAX.  Strict '<', as in the reference's comparisons
+ * (miner.go:56, server.go:273).
+ *
+ * The call stops early and stays exact: the kernels share one stop word per
+ * device (the lowest qualifying nonce published so far), waves skip every
+ * task above it, and the host enqueues launches in ascending order, at most
+ * four in flight, and stops once a hit is known and everything not yet
+ * issued lies above it (DESIGN.md "First below target").  Over [0, 2^64-1]
+ * it returns as soon as the first hit is confirmed.
+ *
+ * Arguments are validated as hm_scan validates them; `out` and `found` are
+ * written only on HM_OK.  An abandoned context returns HM_ERR_TIMEOUT.
+ * HM_OPT_DEADLINE_MS applies (auto models the whole range: an upper bound),
+ * HM_OPT_FORCE_GENERIC and HM_OPT_GRID_PER_CU are honoured; the stream,
+ * fused and RCCL options do not apply: find uses stream 0, one launch per
+ * segment piece, and a host merge (the lowest nonce wins).  hm_find does not
+ * change what hm_scan_stats reports. */
+int hm_find(hm_ctx *ctx, const uint8_t *msg, size_t len, uint64_t lo, uint64_t hi,
+            uint64_t target, hm_result *out, int *found);
+
+/* The same answer as hm_find on the host's cores, no GPU (as hm_scan_cpu is
+ * to hm_scan; `threads` as there).  Threads take ascending windows of the
+ * range from a shared counter and stop at windows above the lowest hit. */
+int hm_find_cpu(const uint8_t *msg, size_t len, uint64_t lo, uint64_t hi, uint64_t target,
+                int threads, hm_result *out, int *found);
+
+/* Work accounting of the most recent successful hm_find on a context.  The
+ * struct only grows at its end. */
+typedef struct hm_find_stats {
+    double wall_ms;           /* host wall time of the call                      */
+    double kernel_ms;         /* summed HIP-event time of its find launches      */
+    uint64_t nonces_enqueued; /* nonces covered by the launches actually issued.
+                                 A chained launch of one epoch out of E over a
+                                 span of tiles counts span / E (the last epoch
+                                 the remainder too): the epochs' even share, as
+                                 hm_stats counts it, not the exact nonces of
+                                 that epoch inside [lo, hi]                      */
+    uint64_t tasks_total;     /* tasks of those launches (a task: one wave's
+                                 64 lanes x a run of loop values; generic: one
+                                 grid-stride step of a wave, 64 nonces)          */
+    uint64_t tasks_run;       /* tasks whose hash loop ran (the others were
+                                 skipped above a published hit)                  */
+    int32_t launches;         /* find-kernel launches issued                     */
+    int32_t ndev;             /* devices of the context                          */
+    int32_t found;            /* the call's *found                               */
+    int32_t reserved;
+} hm_find_stats;
+#define HM_FIND_STATS_SIZE_1_10 56 /* ABI 1.10 */
+
+/* Writes at most `size` bytes (pass sizeof the struct as the caller compiled
+ * it; >= HM_FIND_STATS_SIZE_1_10) of the last successful find's stats;
+ * HM_ERR_INVALID before the first one. */
+int hm_find_stats_sized(const hm_ctx *ctx, hm_find_stats *out, size_t size);
 
 int hm_set_option(hm_ctx *ctx, int opt, int64_t value);
 

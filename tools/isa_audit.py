@@ -5,7 +5,14 @@ tiled and chained kernels).
 
 usage: make -C distributed_bitcoinminer_amd/csrc asm
        python tools/isa_audit.py build/hipminer/scan_kernels.aligned.s > profiles/r03/isa_audit.txt
+       python tools/isa_audit.py --loop=last-big build/hipminer/find_kernels.aligned.s
 (the scan kernels as shipped, after the placement pass align_loops.py)
+
+The hot loop is the kernel's last innermost loop, which it is in the scan
+kernels.  The hm_find kernels end on a short loop of their own (the
+publication's atomic), so for them --loop=last-big takes the last innermost
+loop with at least 300 VALU instructions instead (the same loop as the
+default in every scan kernel).
 
 lane-spill-ops counts the v_writelane/v_readlane instructions SGPR spills
 compile into, in the whole kernel and inside its hot loop.
@@ -38,20 +45,37 @@ def metadata(text):
     return out
 
 
-def loop_mix(lines, start, end):
+BIG_LOOP = 300  # VALU instructions: far above any loop but a SHA-256 compression's
+
+
+def hot_span(body, big=False):
+    """(header, stop) line indices into body of the hot loop: from its
+    'Inner Loop Header' to the s_cbranch_vccz that closes the per-nonce
+    body.  The last innermost loop, or with `big` the last one holding at
+    least BIG_LOOP VALU instructions."""
+    spans = []
+    for hdr in (i for i, l in enumerate(body) if "Inner Loop Header" in l):
+        stop = next((i for i in range(hdr, len(body)) if "s_cbranch_vccz" in body[i]), None)
+        spans.append((hdr, stop))
+    if not spans:
+        return None
+    if not big:
+        return spans[-1] if spans[-1][1] is not None else None
+    valu = lambda sp: sum(1 for l in body[sp[0]:sp[1]] if re.match(r"\s+v_", l))  # noqa: E731
+    spans = [sp for sp in spans if sp[1] is not None and valu(sp) >= BIG_LOOP]
+    return spans[-1] if spans else None
+
+
+def loop_mix(lines, start, end, big=False):
     body = lines[start:end]
-    hdrs = [i for i, l in enumerate(body) if "Inner Loop Header" in l]
-    if not hdrs:
+    span = hot_span(body, big)
+    if span is None:
         return None
-    hdr = max(hdrs)
-    stop = next((i for i in range(hdr, len(body)) if "s_cbranch_vccz" in body[i]), None)
-    if stop is None:
-        return None
-    ops = [l.split()[0] for l in body[hdr:stop] if re.match(r"\s+v_", l)]
+    ops = [l.split()[0] for l in body[span[0]:span[1]] if re.match(r"\s+v_", l)]
     return collections.Counter(ops)
 
 
-def lane_spills(lines, start, end):
+def lane_spills(lines, start, end, big=False):
     """(in the hot loop, in the whole kernel) counts of the v_writelane /
     v_readlane pairs SGPR spills to VGPR lanes compile into."""
     body = lines[start:end]
@@ -59,12 +83,12 @@ def lane_spills(lines, start, end):
     lane = [i for i, l in enumerate(body) if re.match(r"\s+v_(read|write)lane_b32", l)]
     if not hdrs:
         return None, len(lane)
-    hdr = max(hdrs)
-    stop = next((i for i in range(hdr, len(body)) if "s_cbranch_vccz" in body[i]), hdr)
+    span = hot_span(body, big)
+    hdr, stop = span if span else (max(hdrs), max(hdrs))
     return sum(1 for i in lane if hdr <= i < stop), len(lane)
 
 
-def main(path):
+def main(path, big=False):
     text = open(path).read()
     lines = text.split("\n")
     meta = metadata(text)
@@ -73,8 +97,10 @@ def main(path):
         m = re.match(r"^(_ZN2hm\w+):", l)
         if m:
             starts[m.group(1)] = i
-    print("gfx950 ISA audit of distributed_bitcoinminer_amd/csrc/scan_kernels.hip "
-          "(hipcc -O3, ROCm 7.2, after align_loops.py; tools/isa_audit.py)")
+    import os
+    print(f"gfx950 ISA audit of {os.path.basename(path)} (distributed_bitcoinminer_amd/csrc/; "
+          "hipcc -O3, ROCm 7.2, after align_loops.py; tools/isa_audit.py"
+          f"{' --loop=last-big' if big else ''})")
     print("inner loop = the per-nonce-iteration body (64 nonces per wave per iteration)\n")
     for sym in sorted(starts):
         if sym not in meta:
@@ -85,8 +111,8 @@ def main(path):
         row = (f"{sym:60s} vgpr={m['vgpr_count']} sgpr={m['sgpr_count']} "
                f"spills={m['vgpr_spill_count']}/{m['sgpr_spill_count']} "
                f"scratch={m['private_segment_fixed_size']}")
-        mix = loop_mix(lines, i0, i1) if ("tiled" in sym or "chained" in sym) else None
-        in_loop, in_kernel = lane_spills(lines, i0, i1)
+        mix = loop_mix(lines, i0, i1, big) if ("tiled" in sym or "chained" in sym) else None
+        in_loop, in_kernel = lane_spills(lines, i0, i1, big)
         if in_kernel:
             row += f" lane-spill-ops={in_kernel} (hot loop: {in_loop})"
         if mix:
@@ -99,4 +125,5 @@ def main(path):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    args = [a for a in sys.argv[1:] if a != "--loop=last-big"]
+    main(args[0], big=len(args) != len(sys.argv) - 1)
