@@ -29,6 +29,10 @@
  *   oracle_miner_eval <- miner.go:50-59 including the `upper := Upper+1`
  *     wrap (:52): Upper == 2^64-1 scans nothing and returns (MaxUint64, 0).
  *
+ *   oracle_find  <- the same loop in its proof-of-work form (what hm_find and
+ *     hm_find_cpu answer): the first nonce of [lo, hi], ascending, whose hash
+ *     is below a target (strict <), or none.
+ *
  * Parity status: the reference ships no golden vectors for this path and its
  * Go toolchain is absent, so this restatement is pinned to FIPS 180-4 KATs
  * and to fixtures produced by an independent Python hashlib restatement
@@ -206,6 +210,70 @@ void oracle_scan(const uint8_t *msg, size_t len, uint64_t lo, uint64_t hi, int t
                  uint64_t *out_hash, uint64_t *out_nonce) {
     uint64_t s, c;
     oracle_scan_sum(msg, len, lo, hi, threads, out_hash, out_nonce, &s, &c);
+}
+
+/* The proof-of-work form of the same loop, the question hm_find answers:
+ *     for n = lo .. hi: if Hash(msg, n) < target: return (Hash, n)
+ * One ascending strict-< loop per thread over its contiguous chunk, stopping
+ * at the chunk's first hit; chunks ascend, so the first chunk with a hit holds
+ * the lowest one.  No chunk looks at another's progress. */
+typedef struct {
+    const uint8_t *msg;
+    size_t len;
+    uint64_t lo, hi; /* inclusive */
+    uint64_t target;
+    int found;
+    uint64_t hash, nonce;
+} o_find_job;
+
+static void *o_find_job_run(void *arg) {
+    o_find_job *j = (o_find_job *)arg;
+    uint8_t *buf = (uint8_t *)malloc(j->len + 32);
+    j->found = 0;
+    uint64_t i = j->lo;
+    for (;;) {
+        uint64_t h = o_hash_buf(j->msg, j->len, i, buf);
+        if (h < j->target) { j->found = 1; j->hash = h; j->nonce = i; break; }
+        if (i == j->hi) break; /* before the increment: hi may be 2^64-1 */
+        i++;
+    }
+    free(buf);
+    return NULL;
+}
+
+/* First nonce of the inclusive [lo, hi] whose hash is below target.  lo > hi
+ * and target == 0 never hit.  Without a hit *out_found = 0 and the pair is
+ * the miner's initial value (MaxUint64, 0). */
+void oracle_find(const uint8_t *msg, size_t len, uint64_t lo, uint64_t hi, uint64_t target,
+                 int threads, uint64_t *out_hash, uint64_t *out_nonce, int *out_found) {
+    *out_hash = MAXU64; *out_nonce = 0; *out_found = 0;
+    if (lo > hi || target == 0) return;
+    if (threads < 1) threads = 1;
+    uint64_t span_m1 = hi - lo;
+    if ((uint64_t)threads - 1 > span_m1) threads = (int)(span_m1 + 1);
+    o_find_job *jobs = (o_find_job *)calloc((size_t)threads, sizeof(o_find_job));
+    pthread_t *tids = (pthread_t *)calloc((size_t)threads, sizeof(pthread_t));
+    /* the chunks of oracle_scan_sum: 0..rr get q + 1 nonces, the rest q */
+    uint64_t q = span_m1 / (uint64_t)threads, rr = span_m1 % (uint64_t)threads;
+    uint64_t start = lo;
+    for (int c = 0; c < threads; c++) {
+        uint64_t cnt_m1 = q - 1u + ((uint64_t)c <= rr ? 1u : 0u); /* modular */
+        jobs[c].msg = msg; jobs[c].len = len; jobs[c].target = target;
+        jobs[c].lo = start; jobs[c].hi = start + cnt_m1;
+        start = start + cnt_m1 + 1;
+    }
+    if (threads == 1) {
+        o_find_job_run(&jobs[0]);
+    } else {
+        for (int c = 0; c < threads; c++) pthread_create(&tids[c], NULL, o_find_job_run, &jobs[c]);
+        for (int c = 0; c < threads; c++) pthread_join(tids[c], NULL);
+    }
+    for (int c = 0; c < threads; c++)
+        if (jobs[c].found) {
+            *out_hash = jobs[c].hash; *out_nonce = jobs[c].nonce; *out_found = 1;
+            break;
+        }
+    free(jobs); free(tids);
 }
 
 /* miner.go:50-59 verbatim semantics, including `upper := Upper + 1` wrapping

@@ -14,6 +14,9 @@ Two independent restatements of the reference hot path live here
   liboracle.so`` (``oracle/hm_oracle.c``: its own FIPS 180-4 SHA-256 and the
   Sprintf formatting), multi-threaded; used for larger parity ranges and as
   the CPU baseline in bench.py.
+* ``py_find`` / ``c_find``: the same two restatements of the proof-of-work
+  form of that loop (the first nonce whose hash is below a target), the
+  reference for hm_find and hm_find_cpu; tests only.
 * ``fast_scan_sum``: ctypes over ``oracle/build/liboracle_fast.so``
   (``oracle/hm_oracle_fast.c``): the same scan with a per-segment midstate,
   in-place ASCII digit increments and the x86 SHA extensions.  Used only in
@@ -59,6 +62,12 @@ def _load():
         lib.oracle_scan_sum.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64,
                                         ctypes.c_uint64, ctypes.c_int] + \
             [ctypes.POINTER(ctypes.c_uint64)] * 4
+        lib.oracle_find.restype = None
+        lib.oracle_find.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64,
+                                    ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int,
+                                    ctypes.POINTER(ctypes.c_uint64),
+                                    ctypes.POINTER(ctypes.c_uint64),
+                                    ctypes.POINTER(ctypes.c_int)]
         lib.oracle_sha256.restype = None
         lib.oracle_sha256.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p]
         _lib = lib
@@ -86,6 +95,17 @@ def py_scan(msg, lo: int, hi: int):
         if h < result:
             result, index = h, i
     return result, index
+
+
+def py_find(msg, lo: int, hi: int, target: int):
+    """The proof-of-work form of miner.go:53-59: (hash, nonce) of the first
+    nonce of the inclusive [lo, hi] whose hash is below target, or None."""
+    m = _b(msg)
+    for i in range(lo, hi + 1):
+        h = int.from_bytes(hashlib.sha256(m + b" " + str(i).encode()).digest()[:8], "big")
+        if h < target:
+            return h, i
+    return None
 
 
 def py_miner_eval(msg, lower: int, upper: int):
@@ -128,6 +148,19 @@ def c_scan_sum(msg, lo: int, hi: int, threads: int = 0):
     _load().oracle_scan_sum(m, len(m), lo, hi, threads, ctypes.byref(h), ctypes.byref(n),
                             ctypes.byref(s), ctypes.byref(c))
     return (int(h.value), int(n.value)), int(s.value), int(c.value)
+
+
+def c_find(msg, lo: int, hi: int, target: int, threads: int = 0):
+    """oracle_find: (hash, nonce) of the lowest nonce of the inclusive
+    [lo, hi] whose hash is below target, or None (the reference for hm_find
+    and hm_find_cpu)."""
+    m = _b(msg)
+    if threads <= 0:
+        threads = min(16, os.cpu_count() or 1)
+    h, n, f = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int(-1)
+    _load().oracle_find(m, len(m), lo, hi, target, threads, ctypes.byref(h), ctypes.byref(n),
+                        ctypes.byref(f))
+    return (int(h.value), int(n.value)) if f.value else None
 
 
 def py_scan_sum(msg, lo: int, hi: int):

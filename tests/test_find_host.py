@@ -3,7 +3,9 @@ is below a target -- the proof-of-work form of the reference loop
 (cmu440/bitcoin/miner/miner.go:46-59 over bitcoin.Hash, hash.go:13-17):
     for n = lo .. hi: if Hash(msg, n) < target: return (Hash, n)
 Checked against hashlib known answers, the committed golden scans and the C
-oracle, with both compressions and several thread counts; the hm_find_stats
+oracle (its min-hash scan, and its own first-hit search c_find at the target
+edges, dense targets and the top nonce -- the reference the GPU path is
+judged by too), with both compressions and several thread counts; the hm_find_stats
 layout and the ABI version; and, once, a ThreadSanitizer build of the host
 search as a stand-alone program.  No GPU needed."""
 import ctypes
@@ -137,6 +139,65 @@ def test_edges(oracle_mod, path):
             h, n = scan(m, lo, hi)
             assert _lib.find_cpu(m, lo, hi, h + 1, threads=3) == (h, n), (d, m)
             assert _lib.find_cpu(m, lo, hi, h, threads=3) is None, (d, m)
+
+
+def target_edges(oracle_mod, m, lo, hi, j):
+    """The targets at which a first-hit search can go wrong, for one range:
+    dense ones (the answer is lo or a neighbour), the edges of the target's
+    high word ((T - 1) >> 32 at 1, 2^32, 2^32 + 1, 2^63, 2^64 - 1), the
+    range's minimum (a miss) and minimum + 1 (a full search), and a strict-<
+    boundary at the arbitrary nonce lo + j."""
+    best = oracle_mod.c_scan(m, lo, hi)[0]
+    return [MAXU64, 2**63] + [2**64 // 10**k for k in range(1, 7)] + \
+        [1, 2**32, 2**32 + 1, best + 1, best, oracle_mod.c_hash(m, lo + j) + 1]
+
+
+def top_nonce_case():
+    """(msg, hash at 2^64-1): the first of b"top-0" .. b"top-3999" whose hash
+    at nonce 2^64-1 is the lowest of the 4000 -- low enough that thousands of
+    nonces below 2^64-1 all hash above it."""
+    h, i = min((py_hash(b"top-%d" % i, MAXU64), i) for i in range(4000))
+    return b"top-%d" % i, h
+
+
+TOP_CLEAR = 4454  # nonces below 2^64-1 hashing at or above top_nonce_case()'s hash
+
+
+def test_target_edges_against_the_oracle(oracle_mod, path):
+    """find_cpu == c_find at every target edge, dense targets included, on
+    ranges across digit boundaries and at the top of the nonce space."""
+    cases = [(b"bradfitz", 0, 12_000, 5_000), (b"thom yorke", 99_000, 104_000, 4_999),
+             (b"x" * 56, 10**11 - 3_000, 10**11 + 3_000, 3_000),
+             (bytes(range(120)), 10**19 - 2_500, 10**19 + 2_500, 17),
+             (b"", MAXU64 - 5_000, MAXU64, 5_000), (b"q", 77, 77, 0)]
+    for m, lo, hi, j in cases:
+        for T in target_edges(oracle_mod, m, lo, hi, j):
+            exp = oracle_mod.c_find(m, lo, hi, T)
+            for t in THREADS:
+                assert _lib.find_cpu(m, lo, hi, T, threads=t) == exp, (m, lo, hi, T, t)
+        # the dense targets answer at lo or next to it
+        assert oracle_mod.c_find(m, lo, hi, MAXU64)[1] in (lo, lo + 1)
+
+
+def test_top_nonce_against_the_oracle(oracle_mod, path):
+    """Nonce 2^64-1 as the only hit of a one-nonce and of a 4455-nonce range,
+    and a lower hit one nonce further down."""
+    m, h = top_nonce_case()
+    assert (m, h) == (b"top-444", 1599801557507019)
+    assert oracle_mod.c_hash(m, MAXU64) == h
+    assert oracle_mod.c_scan(m, MAXU64 - TOP_CLEAR, MAXU64 - 1)[0] >= h
+    lower = MAXU64 - TOP_CLEAR - 1
+    assert oracle_mod.c_hash(m, lower) < h
+    for t in THREADS:
+        for lo in (MAXU64, MAXU64 - TOP_CLEAR):
+            assert _lib.find_cpu(m, lo, MAXU64, h + 1, threads=t) == (h, MAXU64) == \
+                oracle_mod.c_find(m, lo, MAXU64, h + 1, threads=t), (lo, t)
+            assert _lib.find_cpu(m, lo, MAXU64, h, threads=t) is None
+            assert oracle_mod.c_find(m, lo, MAXU64, h, threads=t) is None
+        for T in (h + 1, h):
+            got = _lib.find_cpu(m, lower, MAXU64, T, threads=t)
+            assert got == (oracle_mod.c_hash(m, lower), lower) == \
+                oracle_mod.c_find(m, lower, MAXU64, T, threads=t), (T, t)
 
 
 def test_invalid_arguments():
