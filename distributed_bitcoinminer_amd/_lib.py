@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes
 import os
 import re
+import struct
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -86,6 +87,19 @@ class hm_find_stats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class hm_collect_stats(ctypes.Structure):
+    """hm_collect_stats of include/hipminer.h (ABI 1.11)."""
+    _fields_ = [("wall_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
+                ("nonces", ctypes.c_uint64), ("total", ctypes.c_uint64),
+                ("launches", ctypes.c_int32), ("ndev", ctypes.c_int32),
+                ("overflow", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+HM_COLLECT_CAP_MAX = 1 << 24
+
 _lib = None
 _lock = threading.Lock()
 
@@ -155,6 +169,17 @@ def load() -> ctypes.CDLL:
         lib.hm_find_stats_sized.restype = ctypes.c_int
         lib.hm_find_stats_sized.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_find_stats),
                                             ctypes.c_size_t]
+        lib.hm_collect.restype = ctypes.c_int
+        lib.hm_collect.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint64,
+                                   ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(hm_result),
+                                   ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)]
+        lib.hm_collect_cpu.restype = ctypes.c_int
+        lib.hm_collect_cpu.argtypes = [u8p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64,
+                                       ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(hm_result),
+                                       ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)]
+        lib.hm_collect_stats_sized.restype = ctypes.c_int
+        lib.hm_collect_stats_sized.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_collect_stats),
+                                               ctypes.c_size_t]
         lib.hm_debug_auto_deadline_ms.restype = ctypes.c_double
         lib.hm_debug_auto_deadline_ms.argtypes = [u8p, ctypes.c_size_t, ctypes.c_uint64,
                                                   ctypes.c_uint64, ctypes.c_int]
@@ -260,6 +285,26 @@ class Context:
             raise HipMinerError(rc, "hm_find_stats_sized")
         return st.as_dict()
 
+    def collect(self, msg, lo: int, hi: int, target: int, cap: int):
+        """hm_collect (ABI 1.11): (total, records).  total = the number of
+        nonces in the inclusive [lo, hi] whose hash is below `target`, always
+        exact; records = every (hash, nonce) of them, ascending by nonce, when
+        total <= cap, and None when total > cap (retry with cap >= total)."""
+        return _collect(lambda m, out, n, tot: self._lib.hm_collect(
+            self._h, m, len(m), lo, hi, target, out, n, tot), "hm_collect", msg, cap)
+
+    def count(self, msg, lo: int, hi: int, target: int) -> int:
+        """hm_collect with no buffer: how many nonces of [lo, hi] hash below `target`."""
+        return self.collect(msg, lo, hi, target, 0)[0]
+
+    def collect_stats(self) -> dict:
+        """hm_collect_stats_sized: work accounting of the last collect on this context."""
+        st = hm_collect_stats()
+        rc = self._lib.hm_collect_stats_sized(self._h, ctypes.byref(st), ctypes.sizeof(st))
+        if rc != HM_OK:
+            raise HipMinerError(rc, "hm_collect_stats_sized")
+        return st.as_dict()
+
     def streams_made(self, device_index: int = 0) -> int:
         """HIP streams (hardware queues) the context has made on its
         device_index-th device (debug export; ABI 1.8 makes them on first use)."""
@@ -316,6 +361,35 @@ def find_cpu(msg, lo: int, hi: int, target: int, threads: int = 0):
     if rc != HM_OK:
         raise HipMinerError(rc, "hm_find_cpu")
     return (int(out.hash), int(out.nonce)) if found.value else None
+
+
+def _collect(call, what: str, msg, cap: int):
+    """Run a collect entry point with a buffer of `cap` records (none for
+    cap = 0) and shape its answer: (total, list of (hash, nonce) or None)."""
+    m = as_bytes(msg)
+    buf = (hm_result * cap)() if cap else None
+    total = ctypes.c_uint64(0)
+    rc = call(m, buf, cap, ctypes.byref(total))
+    if rc != HM_OK:
+        raise HipMinerError(rc, what)
+    t = int(total.value)
+    if t > cap:
+        return t, None
+    if t == 0:
+        return 0, []
+    words = struct.unpack_from(f"={2 * t}Q", buf)
+    return t, list(zip(words[0::2], words[1::2]))
+
+
+def collect_cpu(msg, lo: int, hi: int, target: int, cap: int, threads: int = 0):
+    """hm_collect_cpu (ABI 1.11): Context.collect's answer on the host's cores."""
+    return _collect(lambda m, out, n, tot: load().hm_collect_cpu(
+        m, len(m), lo, hi, target, threads, out, n, tot), "hm_collect_cpu", msg, cap)
+
+
+def count_cpu(msg, lo: int, hi: int, target: int, threads: int = 0) -> int:
+    """hm_collect_cpu with no buffer: Context.count's answer on the host's cores."""
+    return collect_cpu(msg, lo, hi, target, 0, threads)[0]
 
 
 def partition(msg, lo: int, hi: int, n: int) -> list:

@@ -14,6 +14,7 @@
 //   multi-device: contiguous shards, then either a host merge of the 16-B
 //          results or an RCCL all-gather of them (HM_OPT_MERGE_RCCL).
 //   hm_find (ABI 1.10): find_locked below, the kernels of find_kernels.hip.
+//   hm_collect (ABI 1.11): collect_locked below, the kernels of collect_kernels.hip.
 //   The scan kernels come from their own code object (scan_kernels.hip ->
 //   align_loops.py -> hipminer_scan.hsaco, embedded by scan_blob.S), loaded
 //   per device with hipModuleLoadData and launched with hipModuleLaunchKernel.
@@ -114,7 +115,7 @@ struct Device {
     uint32_t* kwt[kStreams] = {};
     uint32_t* aux[kStreams] = {};      // fused launches: s0 / trailer / K+W tables
     uint64_t kwt_rows[kStreams] = {};  // rows allocated (grown on demand, kw_table_rows)
-    std::vector<uint32_t*> retired;    // tables replaced by larger ones, freed at hm_close
+    std::vector<void*> retired;        // tables and buffers replaced by larger ones, freed at hm_close
     uint64_t* cand[kStreams] = {};
     unsigned int* counter[kStreams] = {};
     uint64_t* sums[kStreams] = {};  // checked scans: per-wave (sum, count) slots
@@ -123,6 +124,11 @@ struct Device {
     uint64_t* result = nullptr;    // [kMaxBatch][2]
     uint64_t* gathered = nullptr;  // [ndev][kMaxBatch][2] (RCCL merge)
     uint64_t* find_ctl = nullptr;  // hm_find: [0] the stop word, [1] tasks run (kernels.hpp FindArgs)
+    // hm_collect: [0] total, [1] slot cursor (kernels.hpp CollectArgs), and the record buffer of
+    // collect_cap records, grown when a larger cap arrives (the old one joins `retired`)
+    uint64_t* collect_ctl = nullptr;
+    uint64_t* collect_buf = nullptr;
+    size_t collect_cap = 0;
     hm_result* host_out = nullptr; // pinned, fine-grained [kMaxBatch]: the 16-B readback slots
     hipEvent_t join[kStreams] = {};
     hipEvent_t gate = nullptr;     // stream 0 reached its last dominant segment
@@ -191,6 +197,8 @@ struct hm_ctx {
     hm_stats last{};
     bool have_find_stats = false;  // hm_find keeps its own record: `last` stays the last scan's
     hm_find_stats last_find{};
+    bool have_collect_stats = false;  // and so does hm_collect
+    hm_collect_stats last_collect{};
 };
 
 namespace {
@@ -244,6 +252,7 @@ int device_init(Device& dv, int ordinal) {
     HIPCHK(hipMalloc(&dv.acc, (size_t)kStreams * 2 * sizeof(uint64_t)));
     HIPCHK(hipMalloc(&dv.result, (size_t)kMaxBatch * 2 * sizeof(uint64_t)));
     HIPCHK(hipMalloc(&dv.find_ctl, 2 * sizeof(uint64_t)));
+    HIPCHK(hipMalloc(&dv.collect_ctl, 2 * sizeof(uint64_t)));
     // pinned readback slots of the 16-B result copies
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&dv.host_out), kMaxBatch * sizeof(hm_result),
                          hipHostMallocMapped | hipHostMallocCoherent));
@@ -269,7 +278,7 @@ void device_free(Device& dv) {
         if (s == 0 && dv.t0) (void)hipEventDestroy(dv.t0);
         if (dv.stream[s]) (void)hipStreamDestroy(dv.stream[s]);
     }
-    for (uint32_t* t : dv.retired) (void)hipFree(t);
+    for (void* t : dv.retired) (void)hipFree(t);
     dv.retired.clear();
     for (hipEvent_t e : dv.evpool) (void)hipEventDestroy(e);
     if (dv.mod) (void)hipModuleUnload(dv.mod);
@@ -279,6 +288,8 @@ void device_free(Device& dv) {
     if (dv.result) (void)hipFree(dv.result);
     if (dv.gathered) (void)hipFree(dv.gathered);
     if (dv.find_ctl) (void)hipFree(dv.find_ctl);
+    if (dv.collect_ctl) (void)hipFree(dv.collect_ctl);
+    if (dv.collect_buf) (void)hipFree(dv.collect_buf);
     if (dv.host_out) (void)hipHostFree(dv.host_out);
     dv.ordinal = -1;
 }
@@ -492,8 +503,8 @@ int kw_table_rows(hm_ctx* ctx, Device& dv, int si, uint64_t rows) {
 
 // ---------------------------------------------------------------------------
 // Argument blocks of the per-segment launches, filled from a SegPlan.  The
-// scan path (enqueue_segment, launch_chained_tiles) and the find path
-// (find_issue) both fill theirs here, so a layout or argument change is made
+// scan path (enqueue_segment, launch_chained_tiles), the find path
+// (find_issue) and the collect path (collect_segment) all fill theirs here, so a layout or argument change is made
 // once.  The output fields (cand, sums) are left null: only the scan sets them.
 // ---------------------------------------------------------------------------
 // The tile planner's arguments for tiles [t, t + nt) of s on stream si.  The
@@ -1284,7 +1295,8 @@ uint64_t hm_hash(const uint8_t* msg, size_t len, uint64_t nonce) {
 //      hm_set_option answers HM_ERR_INVALID; the wave-timeline debug export removed;
 //      test and experiment hooks and hm_debug_* prototypes moved to hipminer_debug.h
 // 1.10: hm_find, hm_find_cpu, hm_find_stats_sized
-int hm_version(void) { return (1 << 16) | 10; }
+// 1.11: hm_collect, hm_collect_cpu, hm_collect_stats_sized
+int hm_version(void) { return (1 << 16) | 11; }
 
 // The digest of the sources this library was built from (build_id.py), kept
 // in the binary behind a tag so tools can read it without loading the library.
@@ -1842,6 +1854,19 @@ int find_fail(hm_ctx* ctx, std::vector<FindDev>& fds, int rc) {
     return rc;
 }
 
+// The deadline of a find or collect call that began at t0 (HM_OPT_DEADLINE_MS;
+// auto models the whole range).
+void call_deadline(hm_ctx* ctx, const hm_request& whole,
+                   std::chrono::steady_clock::time_point t0) {
+    ctx->has_deadline = ctx->deadline_opt != 0;
+    ctx->deadline_ms = !ctx->has_deadline ? 0.0
+                       : ctx->deadline_opt > 0 ? (double)ctx->deadline_opt
+                                               : auto_deadline_ms(ctx, &whole, 1);
+    if (ctx->has_deadline)
+        ctx->deadline_at = t0 + std::chrono::duration_cast<std::chrono::steady_clock::duration>(
+                                    std::chrono::duration<double, std::milli>(ctx->deadline_ms));
+}
+
 // hm_find with ctx->mu held.
 int find_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
                 uint64_t target, hm_result* out, int* found) {
@@ -1850,14 +1875,7 @@ int find_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64
     static const uint8_t empty_msg = 0;
     const uint8_t* m = msg ? msg : &empty_msg;
     const size_t mlen = msg ? len : 0;
-    const hm_request whole{m, mlen, lo, hi};
-    ctx->has_deadline = ctx->deadline_opt != 0;
-    ctx->deadline_ms = !ctx->has_deadline ? 0.0
-                       : ctx->deadline_opt > 0 ? (double)ctx->deadline_opt
-                                               : auto_deadline_ms(ctx, &whole, 1);
-    if (ctx->has_deadline)
-        ctx->deadline_at = t0 + std::chrono::duration_cast<std::chrono::steady_clock::duration>(
-                                    std::chrono::duration<double, std::milli>(ctx->deadline_ms));
+    call_deadline(ctx, hm_request{m, mlen, lo, hi}, t0);
     const int ndev = (int)ctx->devs.size();
     FindTally tally;
     uint64_t best = ~0ull, run = 0;
@@ -1948,6 +1966,292 @@ int find_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64
     return HM_OK;
 }
 
+// ---------------------------------------------------------------------------
+// hm_collect: every nonce of [lo, hi] whose hash is below `target`, and their
+// exact count (collect_kernels.hip has the device protocol and its three
+// invariants).
+//
+// Host side.  The range is planned and sharded as find's: plan_range, each
+// digit segment one piece (several devices: pieces of kFindPieceNonces per
+// device, cut at tile boundaries and split with partition_range).  There is no
+// early exit, so there is no lookahead window either: every launch of every
+// device is enqueued on its stream 0 before the host waits on any -- one
+// host_wait per device, no mid-call syncs -- and then each device's total,
+// cursor and min(total, cap) records are read back.  The totals are summed;
+// if the sum fits `cap` the records are concatenated and sorted by nonce.
+// ---------------------------------------------------------------------------
+const char* collect_chained_symbol() {
+    return "_ZN2hm25hm_collect_chained_kernelENS_18CollectChainedArgsE";
+}
+const char* collect_generic_symbol() {
+    return "_ZN2hm25hm_collect_generic_kernelENS_18CollectGenericArgsE";
+}
+std::string collect_tiled_symbol(const SegPlan& s) {
+    char b[128];
+    snprintf(b, sizeof b, "_ZN2hm23hm_collect_tiled_kernelILi%dELb%dELb%dEEEvNS_16CollectTiledArgsE",
+             s.W1, s.straddle ? 1 : 0, s.trailer ? 1 : 0);
+    return b;
+}
+
+// One device's share of a collect call.
+struct CollectDev {
+    hipEvent_t first = nullptr, last = nullptr;  // around its launches
+    uint64_t nonces = 0;
+    int launches = 0;
+};
+
+// Make dv's record buffer hold `cap` records.  A larger one replaces it (at
+// least twice the old size, so all the buffers a device retires together are
+// smaller than its current one); the old buffer is kept until hm_close, as
+// the K+W tables are (hipFree would wait for the whole device).
+int collect_buffer(Device& dv, size_t cap) {
+    if (cap <= dv.collect_cap) return HM_OK;
+    const size_t want = std::min<size_t>(std::max(cap, 2 * dv.collect_cap), HM_COLLECT_CAP_MAX);
+    uint64_t* b = nullptr;
+    if (hipMalloc(&b, want * sizeof(hm_result)) != hipSuccess) {
+        (void)hipGetLastError();
+        return HM_ERR_NOMEM;
+    }
+    if (dv.collect_buf) dv.retired.push_back(dv.collect_buf);
+    dv.collect_buf = b;
+    dv.collect_cap = want;
+    return HM_OK;
+}
+
+// Launch collect kernel fn with its argument block on the device's stream 0
+// (its first launch of the call after the `first` timing event).
+template <typename Args>
+int collect_launch(Device& dv, CollectDev& cd, const Device::Fn& fn, const Args& a, int grid,
+                   uint64_t nonces) {
+    hipStream_t st = dv.stream[0];
+    if (!cd.first) {
+        int rc = next_event(dv, &cd.first);
+        if (rc) return rc;
+        rc = next_event(dv, &cd.last);
+        if (rc) return rc;
+        HIPCHK(hipEventRecord(cd.first, st));
+    }
+    int rc = launch_scan(fn, a, grid, st);
+    if (rc) return rc;
+    cd.nonces += nonces;
+    ++cd.launches;
+    return HM_OK;
+}
+
+// Enqueue every launch of segment `plan` on dv's stream 0: the scan path's
+// launches (enqueue_segment, enqueue_chained) with the collect kernels, the
+// argument blocks filled by the shared helpers plus CollectArgs.
+int collect_segment(hm_ctx* ctx, Device& dv, CollectDev& cd, const MsgPlan& mp,
+                    const SegPlan& plan, const CollectArgs& ka) {
+    hipStream_t st = dv.stream[0];
+    SegPlan s = plan;
+    const Device::Fn* fn = nullptr;
+    int rc;
+    if (s.kind == HM_KIND_GENERIC) {
+        rc = scan_fn(dv, collect_generic_symbol(), &fn);
+        if (rc) return rc;
+        for (uint64_t g = s.lo;;) {
+            CollectGenericArgs a;
+            generic_args(mp, s, g, std::min<uint64_t>(s.hi - g, kFindGenericNonces - 1), a.g);
+            a.k = ka;
+            const uint64_t count_m1 = a.g.count_m1;
+            rc = collect_launch(dv, cd, *fn, a, generic_grid(dv, count_m1), count_m1 + 1);
+            if (rc) return rc;
+            if (s.hi - g == count_m1) return HM_OK;
+            g += count_m1 + 1;
+        }
+    }
+    const bool ch = s.kind == HM_KIND_CHAINED;
+    uint64_t nep = 1, nloop = 0;
+    uint32_t kw[64] = {0};
+    if (ch) {
+        rc = chained_table(ctx, dv, 0, s);
+        if (rc) return rc;
+        nloop = pow10_u64(s.fe);
+        nep = pow10_u64(s.f - s.fe);
+        rc = scan_fn(dv, collect_chained_symbol(), &fn);
+    } else {
+        if (s.trailer) trailer_kw(s, kw);
+        rc = scan_fn(dv, collect_tiled_symbol(s), &fn);
+    }
+    if (rc) return rc;
+    const uint64_t max_tiles = max_launch_tiles(s);
+    for (uint64_t e = 0; e < nep; ++e) {
+        if (ch) HIPCHK(launch_kw_table(dv.kwt[0], s.f, s.fe, e * nloop, s.total_bits, st));
+        for (uint64_t t = s.tile_lo; t <= s.tile_hi;) {
+            const uint64_t nt = std::min<uint64_t>(max_tiles, s.tile_hi - t + 1);
+            const uint64_t span = tile_span_nonces(s, t, nt);
+            uint32_t unit0, ntasks;
+            uint64_t nunits;
+            int grid;
+            HIPCHK(launch_tile_plan(plan_args(dv, mp, s, 0, t, nt), st));
+            if (ch) {
+                CollectChainedArgs a;
+                chained_args(ctx, dv, s, 0, t, nt, e, nep, a.c, &unit0, &nunits);
+                a.k = ka;
+                rc = queue_tasks(ctx, dv, *fn, 0, nunits, unit0, &a.c.ntasks, &a.c.nbig, &ntasks,
+                                 &grid);
+                if (rc) return rc;
+                // the epochs split every lane value's nonces evenly (stats only)
+                rc = collect_launch(dv, cd, *fn, a, grid,
+                                    span / nep + (e + 1 == nep ? span % nep : 0));
+            } else {
+                CollectTiledArgs a;
+                tiled_args(ctx, dv, s, 0, t, nt, kw, a.t, &unit0, &nunits);
+                a.k = ka;
+                rc = queue_tasks(ctx, dv, *fn, 0, nunits, unit0, &a.t.ntasks, &a.t.nbig, &ntasks,
+                                 &grid);
+                if (rc) return rc;
+                rc = collect_launch(dv, cd, *fn, a, grid, span);
+            }
+            if (rc) return rc;
+            t += nt;
+            if (t == 0) break;  // tile index wrapped (cannot happen for d <= 20)
+        }
+    }
+    return HM_OK;
+}
+
+// A collect that fails part-way leaves nothing behind, as a find (find_fail).
+int collect_fail(hm_ctx* ctx, int rc) {
+    if (rc == HM_ERR_TIMEOUT || ctx->abandoned) return rc;
+    for (Device& dv : ctx->devs) {
+        if (hipSetDevice(dv.ordinal) == hipSuccess && host_wait(ctx, dv.stream[0]) != HM_OK) break;
+        dv.evnext = 0;
+    }
+    return rc;
+}
+
+// hm_collect with ctx->mu held.  *recs: the records, ascending by nonce, when
+// *total <= cap; empty otherwise.
+int collect_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
+                   uint64_t target, size_t cap, std::vector<hm_result>* recs, uint64_t* total) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (ctx->abandoned) return HM_ERR_TIMEOUT;
+    static const uint8_t empty_msg = 0;
+    const uint8_t* m = msg ? msg : &empty_msg;
+    const size_t mlen = msg ? len : 0;
+    call_deadline(ctx, hm_request{m, mlen, lo, hi}, t0);
+    const int ndev = (int)ctx->devs.size();
+    std::vector<CollectDev> cds(ndev);
+    uint64_t sum = 0;
+    double kernel_ms = 0;
+    recs->clear();
+    if (lo <= hi && target != 0) {
+        const MsgPlan mp = plan_message(m, mlen);
+        for (auto& dv : ctx->devs) {
+            HIPCHK(hipSetDevice(dv.ordinal));
+            dv.evnext = 0;
+            int rc = collect_buffer(dv, cap);
+            if (rc) return rc;
+            // the total and the slot cursor start at 0
+            HIPCHK(hipMemsetAsync(dv.collect_ctl, 0, 2 * sizeof(uint64_t), dv.stream[0]));
+        }
+        for (const SegPlan& seg : plan_range(mp, lo, hi, ctx->force_generic, ctx->table_digits)) {
+            uint64_t span = ~0ull;  // one device: the segment is one piece
+            if (ndev > 1) {
+                span = kFindPieceNonces * (uint64_t)ndev;
+                if (seg.pow10V > 1) span = std::max<uint64_t>(span / seg.pow10V, 1) * seg.pow10V;
+            }
+            for (uint64_t a = seg.lo;;) {
+                // pieces end at multiples of span (tile boundaries)
+                const uint64_t k = a / span;
+                const uint64_t b =
+                    ndev == 1 || k >= ~0ull / span ? seg.hi : std::min(seg.hi, (k + 1) * span - 1);
+                const std::vector<Shard> sh = partition_range(mp, a, b, ndev, ctx->force_generic);
+                for (int i = 0; i < ndev; ++i) {
+                    if (sh[i].empty) continue;
+                    Device& dv = ctx->devs[i];
+                    if (hipSetDevice(dv.ordinal) != hipSuccess) return collect_fail(ctx, HM_ERR_HIP);
+                    CollectArgs ka;
+                    ka.total = dv.collect_ctl;
+                    ka.cursor = dv.collect_ctl + 1;
+                    ka.out = cap ? dv.collect_buf : nullptr;
+                    ka.target = target;
+                    ka.cap = (uint32_t)cap;
+                    for (const SegPlan& s : plan_range(mp, sh[i].lo, sh[i].hi, ctx->force_generic,
+                                                       ctx->table_digits)) {
+                        int rc = collect_segment(ctx, dv, cds[i], mp, s, ka);
+                        if (rc) return collect_fail(ctx, rc);
+                    }
+                }
+                if (b == seg.hi) break;
+                a = b + 1;
+            }
+        }
+        for (int i = 0; i < ndev; ++i) {
+            if (!cds[i].first) continue;
+            Device& dv = ctx->devs[i];
+            if (hipSetDevice(dv.ordinal) != hipSuccess ||
+                hipEventRecord(cds[i].last, dv.stream[0]) != hipSuccess)
+                return collect_fail(ctx, HM_ERR_HIP);
+        }
+        // everything is enqueued: wait for each device, then read it back
+        std::vector<uint64_t> dev_total(ndev, 0);
+        for (int i = 0; i < ndev; ++i) {
+            Device& dv = ctx->devs[i];
+            if (hipSetDevice(dv.ordinal) != hipSuccess) return collect_fail(ctx, HM_ERR_HIP);
+            int rc = host_wait(ctx, dv.stream[0]);
+            if (rc) return collect_fail(ctx, rc);
+        }
+        for (int i = 0; i < ndev; ++i) {
+            Device& dv = ctx->devs[i];
+            HIPCHK(hipSetDevice(dv.ordinal));
+            uint64_t ctl[2];
+            int rc = host_read(ctx, ctl, dv.collect_ctl, sizeof ctl);
+            if (rc) return rc;
+            dev_total[i] = ctl[0];
+            // a device whose records all fit reserved exactly one slot per hit
+            if (cap && ctl[0] <= cap && ctl[1] != ctl[0]) return HM_ERR_INTERNAL;
+            if (sum + ctl[0] < sum) return HM_ERR_INTERNAL;
+            sum += ctl[0];
+            if (cds[i].first) {
+                float ms = 0.f;
+                HIPCHK(hipEventElapsedTime(&ms, cds[i].first, cds[i].last));
+                kernel_ms += ms;
+            }
+            dv.evnext = 0;  // the events are free again
+        }
+        if (sum <= cap && sum > 0) {
+            recs->resize((size_t)sum);
+            size_t at = 0;
+            for (int i = 0; i < ndev; ++i) {
+                if (!dev_total[i]) continue;
+                Device& dv = ctx->devs[i];
+                HIPCHK(hipSetDevice(dv.ordinal));
+                int rc = host_read(ctx, recs->data() + at, dv.collect_buf,
+                                   (size_t)dev_total[i] * sizeof(hm_result));
+                if (rc) return rc;
+                at += (size_t)dev_total[i];
+            }
+            // slots are handed out in dispatch order: the answer is in nonce order
+            std::sort(recs->begin(), recs->end(),
+                      [](const hm_result& x, const hm_result& y) { return x.nonce < y.nonce; });
+            for (size_t i = 0; i < recs->size(); ++i) {
+                const hm_result& r = (*recs)[i];
+                if (r.hash >= target || r.nonce < lo || r.nonce > hi ||
+                    (i > 0 && r.nonce == (*recs)[i - 1].nonce))
+                    return HM_ERR_INTERNAL;
+            }
+        }
+    }
+    hm_collect_stats st{};
+    st.kernel_ms = kernel_ms;
+    st.total = sum;
+    st.ndev = ndev;
+    st.overflow = sum > cap ? 1 : 0;
+    for (const CollectDev& cd : cds) {
+        st.nonces += cd.nonces;
+        st.launches += cd.launches;
+    }
+    st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
+                     .count();
+    ctx->last_collect = st;
+    ctx->have_collect_stats = true;
+    *total = sum;
+    return HM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2010,6 +2314,30 @@ int hm_find_stats_sized(const hm_ctx* ctx, hm_find_stats* out, size_t size) {
     std::lock_guard<std::mutex> g(ctx->mu);
     if (!ctx->have_find_stats) return HM_ERR_INVALID;
     memcpy(out, &ctx->last_find, std::min(size, sizeof(hm_find_stats)));
+    return HM_OK;
+}
+
+int hm_collect(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
+               uint64_t target, hm_result* out, size_t cap, uint64_t* total) {
+    if (!ctx || !total || (!msg && len) || cap > HM_COLLECT_CAP_MAX || (cap && !out))
+        return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    std::vector<hm_result> recs;
+    uint64_t sum = 0;
+    int rc = guarded(
+        [&] { return collect_locked(ctx, msg, len, lo, hi, target, cap, &recs, &sum); });
+    if (rc) return rc;
+    // sum > cap: out is not written at all
+    if (sum <= cap && sum) memcpy(out, recs.data(), (size_t)sum * sizeof(hm_result));
+    *total = sum;
+    return HM_OK;
+}
+
+int hm_collect_stats_sized(const hm_ctx* ctx, hm_collect_stats* out, size_t size) {
+    if (!ctx || !out || size < HM_COLLECT_STATS_SIZE_1_11) return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!ctx->have_collect_stats) return HM_ERR_INVALID;
+    memcpy(out, &ctx->last_collect, std::min(size, sizeof(hm_collect_stats)));
     return HM_OK;
 }
 

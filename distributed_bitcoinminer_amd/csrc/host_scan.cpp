@@ -1,5 +1,6 @@
-// host_scan.cpp -- hm_scan_cpu and hm_find_cpu: the min-hash scan, and the
-// first-below-target search (ABI 1.10), on the host's cores.
+// host_scan.cpp -- hm_scan_cpu, hm_find_cpu and hm_collect_cpu: the min-hash
+// scan, the first-below-target search (ABI 1.10) and the all-below-target
+// collection (ABI 1.11), on the host's cores.
 //
 // SURVEY §8(b)'s liveness path.  The reference miner always answers a
 // Request with a Result (cmu440/bitcoin/miner/miner.go:60-62); a GPU miner
@@ -206,6 +207,28 @@ void find_worker(const MsgPlan& mp, uint64_t lo, uint64_t hi, uint64_t target, u
     }
 }
 
+// hm_collect_cpu's share of one thread: the records of its contiguous chunk,
+// ascending (the walk's order), and their count.  Once the chunk alone holds
+// more than `cap` hits the call has overflowed and its records will not be
+// returned: the thread stops storing and keeps counting.
+struct CollectPart {
+    std::vector<hm_result> recs;
+    uint64_t count = 0;
+    bool failed = false;  // out of memory
+};
+
+void collect_chunk(const MsgPlan& mp, uint64_t a, uint64_t b, uint64_t target, size_t cap,
+                   CompressFn compress, CollectPart* out) {
+    try {
+        walk_chunk(mp, a, b, compress, [&](uint64_t k, uint64_t n) {
+            if (k < target && ++out->count <= cap) out->recs.push_back(hm_result{k, n});
+            return false;
+        });
+    } catch (...) {
+        out->failed = true;
+    }
+}
+
 // Default thread count: the CPUs this process may run on.  A GPU box's
 // per-GPU share is an affinity set inside a machine whose
 // hardware_concurrency() counts every CPU, many times more.
@@ -311,6 +334,72 @@ extern "C" int hm_find_cpu(const uint8_t* msg, size_t len, uint64_t lo, uint64_t
             *out = hm_result{~0ull, 0};
             *found = 0;
         }
+        return HM_OK;
+    } catch (const std::bad_alloc&) {
+        return HM_ERR_NOMEM;
+    } catch (...) {
+        return HM_ERR_INTERNAL;
+    }
+}
+
+extern "C" int hm_collect_cpu(const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
+                              uint64_t target, int threads, hm_result* out, size_t cap,
+                              uint64_t* total) {
+    using namespace hm;
+    if (!total || (!msg && len) || cap > HM_COLLECT_CAP_MAX || (cap && !out))
+        return HM_ERR_INVALID;
+    try {
+        if (lo > hi || target == 0) {
+            *total = 0;
+            return HM_OK;
+        }
+        static const uint8_t empty = 0;
+        const MsgPlan mp = plan_message(msg ? msg : &empty, msg ? len : 0);
+        const CompressFn compress = pick_compress();
+        // contiguous, near-equal chunks in ascending order, as hm_scan_cpu's
+        typedef unsigned __int128 u128;
+        const u128 count = (u128)(hi - lo) + 1;
+        unsigned n = threads > 0 ? (unsigned)threads : default_threads();
+        n = std::min(n, 1024u);
+        if (count < (u128)n * 4096) n = (unsigned)std::max<u128>(1, count / 4096);
+        std::vector<CollectPart> part(n);
+        std::vector<std::thread> pool;
+        pool.reserve(n);
+        const u128 per = count / n, extra = count % n;
+        u128 start = 0;
+        int rc = HM_OK;
+        for (unsigned t = 0; t < n; ++t) {
+            const u128 len_t = per + (t < extra ? 1 : 0);
+            const uint64_t a = lo + (uint64_t)start, b = lo + (uint64_t)(start + len_t - 1);
+            start += len_t;
+            if (t + 1 == n) {
+                collect_chunk(mp, a, b, target, cap, compress, &part[t]);  // the calling thread
+                break;
+            }
+            try {
+                pool.emplace_back(collect_chunk, std::cref(mp), a, b, target, cap, compress,
+                                  &part[t]);
+            } catch (...) {  // no thread: join the started ones before failing
+                rc = HM_ERR_INTERNAL;
+                break;
+            }
+        }
+        for (auto& th : pool) th.join();
+        if (rc) return rc;
+        uint64_t sum = 0;
+        for (const CollectPart& p : part) {
+            if (p.failed) return HM_ERR_NOMEM;
+            sum += p.count;  // <= hi - lo + 1; 2^64 hits of [0, 2^64-1] are beyond any run
+        }
+        if (sum <= cap) {
+            // the chunks ascend and each is ascending: so is the concatenation
+            size_t at = 0;
+            for (const CollectPart& p : part) {
+                if (!p.recs.empty()) memcpy(out + at, p.recs.data(), p.recs.size() * sizeof(hm_result));
+                at += p.recs.size();
+            }
+        }
+        *total = sum;
         return HM_OK;
     } catch (const std::bad_alloc&) {
         return HM_ERR_NOMEM;

@@ -238,6 +238,34 @@ struct FindGenericArgs {
     FindArgs f;
 };
 
+// ---------------------------------------------------------------------------
+// hm_collect (collect_kernels.hip, DESIGN.md "All below target"): every nonce
+// whose hash is below a target, and their exact count.  Two 64-bit words per
+// device, zeroed before a call's first launch: `total` (each wave adds its
+// hit count once, at its exit) and `cursor` (the next free record slot; one
+// fetch_add per wave step with hits).  The collect kernels take the scan
+// kernel's argument block (cand and sums unused) plus this one.
+// ---------------------------------------------------------------------------
+struct CollectArgs {
+    uint64_t* total;   // += the wave's hits, once per wave
+    uint64_t* cursor;  // slot reservations (cap > 0 only)
+    uint64_t* out;     // cap records of 2 x u64 (hash, nonce); null when cap == 0
+    uint64_t target;   // >= 1
+    uint32_t cap;      // <= HM_COLLECT_CAP_MAX
+};
+struct CollectTiledArgs {
+    TiledArgs t;
+    CollectArgs k;
+};
+struct CollectChainedArgs {
+    ChainedArgs c;
+    CollectArgs k;
+};
+struct CollectGenericArgs {
+    GenericArgs g;
+    CollectArgs k;
+};
+
 // Launchers of the auxiliary kernels (kernels.hip; return hipError_t of the
 // launch).  The scan kernels (scan_kernels.hip: hm_tiled_kernel<W1,
 // STRADDLE, TRAILER>, hm_chained_kernel, hm_generic_kernel and their

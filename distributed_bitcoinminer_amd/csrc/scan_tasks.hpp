@@ -31,9 +31,11 @@ struct WaveSums {
 // the wave's best.  `cand` is h0 <= best.hi (the caller's one compare per
 // nonce); only when some lane holds one does the 64-lane reduce run, and
 // only then are the nonce and its range check formed.  Lanes outside
-// [seg_lo, seg_hi] never win.
+// [seg_lo, seg_hi] never win.  The last argument is lane_ok, false on a
+// surplus lane (one that repeats another lane's nonce): a duplicate cannot
+// change a minimum, so only WaveCollect below looks at it.
 DEV void take_step(WaveBest& best, bool cand, uint32_t h0, uint32_t h1, uint64_t nbase,
-                   uint32_t off, uint64_t seg_lo, uint64_t seg_hi) {
+                   uint32_t off, uint64_t seg_lo, uint64_t seg_hi, bool = true) {
     if (__builtin_amdgcn_ballot_w64(cand)) {
         uint64_t key = ((uint64_t)h0 << 32) | h1;
         uint64_t nn = nbase + off;
@@ -70,7 +72,7 @@ struct WaveFirst {
 };
 DEV bool wave_cand(const WaveFirst& first, uint32_t h0) { return h0 <= first.thi; }
 DEV void take_step(WaveFirst& first, bool cand, uint32_t h0, uint32_t h1, uint64_t nbase,
-                   uint32_t off, uint64_t seg_lo, uint64_t seg_hi) {
+                   uint32_t off, uint64_t seg_lo, uint64_t seg_hi, bool) {
     if (__builtin_amdgcn_ballot_w64(cand)) {
         const uint64_t key = ((uint64_t)h0 << 32) | h1;
         uint64_t nn = nbase + off;
@@ -81,6 +83,65 @@ DEV void take_step(WaveFirst& first, bool cand, uint32_t h0, uint32_t h1, uint64
         wave_min(nn, zero);
         nn = uni64(nn);
         if (nn < first.nonce) first.nonce = nn;
+    }
+}
+
+// "All below target" reduction (collect_kernels.hip, hm_collect): the wave
+// counts every nonce n in [seg_lo, seg_hi] with Hash(msg, n) < target and,
+// with a record buffer (cap > 0), appends (hash, nonce) for each.  The
+// per-nonce test is WaveFirst's one compare.  Behind the ballot the 64-bit
+// key, key < target, the range check and lane_ok are formed -- a surplus lane
+// (one that repeats another lane's nonce) is never a hit: a duplicate cannot
+// hurt a minimum but would be counted twice here -- the hits of the step are
+// counted in a wave-uniform register (popcount of the ballot), and one lane
+// reserves that many slots with one atomic on the device's cursor, each hit
+// lane taking base + its rank among the hit lanes.  A wave that sees a base
+// at or past cap stops reserving: the call has overflowed and its records
+// will not be read.
+struct WaveCollect {
+    uint32_t thi;      // (target - 1) >> 32, target >= 1
+    uint32_t cap;      // records the buffer holds; 0: count only
+    uint64_t target;
+    uint64_t* cursor;  // next free slot (agent scope)
+    uint64_t* out;     // 2 x u64 per slot: (hash, nonce)
+    uint64_t count = 0;  // the wave's hits (uniform)
+    bool full = false;   // a reservation of this wave began at or past cap (uniform)
+};
+DEV bool wave_cand(const WaveCollect& c, uint32_t h0) { return h0 <= c.thi; }
+DEV void take_step(WaveCollect& c, bool cand, uint32_t h0, uint32_t h1, uint64_t nbase,
+                   uint32_t off, uint64_t seg_lo, uint64_t seg_hi, bool lane_ok) {
+    if (__builtin_amdgcn_ballot_w64(cand)) {
+        const uint64_t key = ((uint64_t)h0 << 32) | h1;
+        const uint64_t nn = nbase + off;
+        const bool ok = cand && lane_ok && key < c.target && nn >= seg_lo && nn <= seg_hi;
+        const uint64_t hits = __builtin_amdgcn_ballot_w64(ok);
+        if (hits) {
+            const uint32_t n = (uint32_t)__builtin_popcountll(hits);
+            c.count += n;
+            if (c.cap != 0 && !c.full) {
+                // hit lanes below this one: a hit lane's rank in the step
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi(
+                    (uint32_t)(hits >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hits, 0u));
+                // the lowest hit lane reserves the step's slots
+                uint64_t base = 0;
+                if (ok && rank == 0)
+                    base = __hip_atomic_fetch_add(c.cursor, (uint64_t)n, __ATOMIC_RELAXED,
+                                                  __HIP_MEMORY_SCOPE_AGENT);
+                // every lane takes the reserving lane's value
+                const uint32_t src = (uint32_t)__builtin_ctzll(hits);
+                base = ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(base >> 32), src) << 32) |
+                       __builtin_amdgcn_readlane((uint32_t)base, src);
+                if (base >= c.cap) {
+                    c.full = true;
+                } else if (ok) {
+                    const uint64_t slot = base + rank;
+                    if (slot < c.cap) {
+                        c.out[2 * slot] = key;
+                        c.out[2 * slot + 1] = nn;
+                    }
+                }
+            }
+        }
     }
 }
 
@@ -156,8 +217,9 @@ DEV uint64_t lane_digits(uint32_t v, uint32_t q) {
 // t0 runs over [t0_begin, t0_end) (the fused launch's split tasks; the
 // per-segment kernels take the constant defaults, so their loop is the full
 // one).  Best is the reduction the task folds its nonces into: WaveBest (the
-// running minimum, the default) or WaveFirst (hm_find); each brings its
-// wave_cand (the one compare per nonce) and take_step.
+// running minimum, the default), WaveFirst (hm_find) or WaveCollect
+// (hm_collect); each brings its wave_cand (the one compare per nonce) and
+// take_step.
 // ---------------------------------------------------------------------------
 template <int W1, bool STRADDLE, bool TRAILER, bool CSUM, typename S0, typename KW,
           typename Best = WaveBest>
@@ -257,7 +319,8 @@ DEV void tiled_task(const uint32_t* __restrict__ R, uint32_t chunk, uint32_t t1_
                     ++sums.cnt;
                 }
             }
-            take_step(best, wave_cand(best, h0), h0, h1, nbase, t1 * 10u + t0, seg_lo, seg_hi);
+            take_step(best, wave_cand(best, h0), h0, h1, nbase, t1 * 10u + t0, seg_lo, seg_hi,
+                      lane_ok);
         }
     }
 }
@@ -310,7 +373,7 @@ DEV void chained_task(const uint32_t* __restrict__ R, uint32_t chunk, uint32_t t
                 ++sums.cnt;
             }
         }
-        take_step(best, wave_cand(best, h0), h0, u.b + cs.b, nbase, t, seg_lo, seg_hi);
+        take_step(best, wave_cand(best, h0), h0, u.b + cs.b, nbase, t, seg_lo, seg_hi, lane_ok);
     }
 }
 

@@ -61,6 +61,27 @@ def merge_first(results):
     return best
 
 
+def merge_collect(parts, cap: int):
+    """Merge of per-shard collect results (``Context.collect`` / ``collect_cpu``:
+    ``(total, records or None)``), given in shard order: ``(sum of the totals,
+    the shards' records concatenated)`` -- ascending by nonce, since the
+    shards of one range ascend and are disjoint -- or ``(sum, None)`` when the
+    sum exceeds ``cap``, as one collect over the whole range with that cap
+    answers.  A shard that overflowed its own buffer although the sum fits
+    ``cap`` was given too small a one: ValueError."""
+    parts = list(parts)
+    total = sum(int(t) for t, _ in parts)
+    if total > cap:
+        return total, None
+    out = []
+    for t, recs in parts:
+        if recs is None:
+            raise ValueError(f"a shard with {t} hits returned no records but the total "
+                             f"{total} fits cap {cap}: collect every shard with cap >= {cap}")
+        out.extend((int(h), int(n)) for h, n in recs)
+    return total, out
+
+
 def _pack(res) -> np.ndarray:
     return np.array([res[0], res[1]], dtype=np.uint64).view(np.int64)
 

@@ -17,7 +17,9 @@
  *
  * hm_find (ABI 1.10) adds the proof-of-work form of that loop, which the
  * reference does not have: the LOWEST nonce whose hash is below a target,
- * found without scanning the rest of the range.
+ * found without scanning the rest of the range.  hm_collect (ABI 1.11) adds
+ * its share-collection form: EVERY nonce whose hash is below a target, and
+ * their exact count.
  *
  * The cgo binding a maintainer adds to the Go miner is in INTEGRATION.md.
  *
@@ -350,6 +352,63 @@ typedef struct hm_find_stats {
  * it; >= HM_FIND_STATS_SIZE_1_10) of the last successful find's stats;
  * HM_ERR_INVALID before the first one. */
 int hm_find_stats_sized(const hm_ctx *ctx, hm_find_stats *out, size_t size);
+
+/* ABI 1.11: share collection.  The result of
+ *   for n = lo .. hi (inclusive): if Hash(msg, n) < target: emit (Hash, n)
+ * *total = the number of such n, always exact (the whole range is always
+ * hashed; strict '<' as in hm_find).
+ *   *total <= cap: out[0 .. *total) holds every (Hash(msg, n), n), ascending
+ *                  by nonce; nothing at or beyond out[*total] is touched.
+ *   *total >  cap: out is not written at all.  The caller retries with
+ *                  cap >= *total or a narrower range (the size-query idiom).
+ *                  No "some cap of them" result is ever returned: the answer
+ *                  never depends on dispatch order.
+ *   cap == 0 with out == NULL is the pure count: the hit rate of the range at
+ *   the target, what a server sets a share difficulty from.
+ * target = 0 and lo > hi give *total = 0.  hi may be UINT64_MAX, and nonce
+ * UINT64_MAX is an ordinary record.
+ *
+ * Arguments are validated as hm_find validates them; cap > HM_COLLECT_CAP_MAX,
+ * cap > 0 with out == NULL, and total == NULL are HM_ERR_INVALID.  `out` and
+ * `*total` are written only on HM_OK.  An abandoned context returns
+ * HM_ERR_TIMEOUT.  HM_OPT_DEADLINE_MS applies, HM_OPT_FORCE_GENERIC and
+ * HM_OPT_GRID_PER_CU are honoured; the stream, fused and RCCL options do not
+ * apply: every launch of every device is enqueued on stream 0 before the host
+ * waits on any, the devices' shards are those of hm_partition (in pieces of
+ * 2^40 nonces per device), and the host concatenates and sorts their records.
+ * The host recomputes nothing: a record carries the hash the kernel formed.
+ * Each device keeps a buffer of `cap` records (16 bytes each), grown when a
+ * larger cap arrives and kept until hm_close.  hm_collect does not change what
+ * hm_scan_stats* or hm_find_stats_sized report. */
+#define HM_COLLECT_CAP_MAX (1u << 24) /* records; 256 MiB of device buffer per device */
+int hm_collect(hm_ctx *ctx, const uint8_t *msg, size_t len, uint64_t lo, uint64_t hi,
+               uint64_t target, hm_result *out, size_t cap, uint64_t *total);
+
+/* The same answer as hm_collect on the host's cores, no GPU (`threads` as
+ * hm_scan_cpu's).  Each thread walks a contiguous chunk, ascending; the
+ * chunks' records are concatenated in order. */
+int hm_collect_cpu(const uint8_t *msg, size_t len, uint64_t lo, uint64_t hi, uint64_t target,
+                   int threads, hm_result *out, size_t cap, uint64_t *total);
+
+/* Work accounting of the most recent successful hm_collect on a context.  The
+ * struct only grows at its end. */
+typedef struct hm_collect_stats {
+    double wall_ms;    /* host wall time of the call                             */
+    double kernel_ms;  /* HIP-event time from each device's first collect launch
+                          to the end of its last, summed over devices            */
+    uint64_t nonces;   /* nonces covered by the launches: hi - lo + 1            */
+    uint64_t total;    /* the call's *total                                      */
+    int32_t launches;  /* collect-kernel launches issued                         */
+    int32_t ndev;      /* devices of the context                                 */
+    int32_t overflow;  /* 1: *total > cap, `out` was not written; else 0         */
+    int32_t reserved;
+} hm_collect_stats;
+#define HM_COLLECT_STATS_SIZE_1_11 48 /* ABI 1.11 */
+
+/* Writes at most `size` bytes (pass sizeof the struct as the caller compiled
+ * it; >= HM_COLLECT_STATS_SIZE_1_11) of the last successful collect's stats;
+ * HM_ERR_INVALID before the first one. */
+int hm_collect_stats_sized(const hm_ctx *ctx, hm_collect_stats *out, size_t size);
 
 int hm_set_option(hm_ctx *ctx, int opt, int64_t value);
 
