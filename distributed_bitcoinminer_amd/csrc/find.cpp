@@ -1,0 +1,217 @@
+// find.cpp -- hm_find (ABI 1.10).
+// ---------------------------------------------------------------------------
+// hm_find: the lowest nonce of [lo, hi] whose hash is below `target`
+// (find_kernels.hip has the device protocol and its three invariants).
+//
+// Host side.  The range is planned with plan_range; each digit segment is
+// one piece (with several devices: pieces of at most kFindPieceNonces per
+// device, cut at tile boundaries and split across the devices with
+// partition_range; PieceWalk).  Pieces are processed in ascending order.
+// Within a piece every device walks its shard's launches (SegWalk) in
+// ascending order on stream 0, at most kFindLookahead in flight: it issues
+// that many, waits for them (host_wait), and reads its stop word and task
+// counter back (host_read).
+// A launch whose smallest nonce is above the lowest hit known so far is
+// never issued, and the call ends once that holds for every launch left: a
+// hit is known, and all work not yet issued lies above it.  A launch
+// already in flight when a hit is published exits on its first read of the
+// word.
+//
+// Chained segments with epochs run epoch by epoch over the same tiles, so
+// their launches are not ascending: launch (e, t) starts at t * 10^V +
+// e * 10^fe.  The rule is applied per launch there -- within an epoch the
+// tiles above the hit are dropped, and the call ends when an epoch's first
+// launch is above it -- and a task's lanes stride 10^f nonces, so a hit
+// prunes only the tasks that start above it: later epochs still run the
+// tasks that start below the hit (their in-range nonces above it are
+// ignored by the wave's bound).  That is the loss of pruning: exactness is
+// unaffected.
+//
+// A hit at nonce MaxUint64 cannot be told from "none" in the stop word, so
+// the kernels never publish it and the host tests that one nonce itself.
+// ---------------------------------------------------------------------------
+#include "hm_internal.hpp"
+
+namespace hm {
+namespace {
+
+constexpr int kFindLookahead = 4;
+
+// One device's walk through its shard of a piece.
+struct FindDev {
+    std::vector<SegPlan> segs;  // the shard's segments (one digit count: one)
+    size_t si = 0;
+    bool seg_open = false;      // `walk` is on segs[si]
+    SegWalk walk;
+    int inflight = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
+    uint64_t word = ~0ull, run = 0;  // last readback
+};
+
+struct FindTally {
+    uint64_t nonces = 0, tasks = 0;
+    int launches = 0;
+    double kernel_ms = 0;
+};
+
+// Issue the device's next launch whose smallest nonce is <= best (the lowest
+// hit known; MaxUint64 = none), between two timing events, and count it.
+// *issued = false: nothing left to issue in this piece.  A pruned launch
+// enqueues nothing.
+int find_issue(hm_ctx* ctx, Device& dv, FindDev& fd, const MsgPlan& mp, uint64_t target,
+               uint64_t best, FindTally& tally, bool* issued) {
+    *issued = false;
+    for (;;) {
+        if (fd.si >= fd.segs.size()) return HM_OK;
+        const SegPlan& s = fd.segs[fd.si];
+        if (!fd.seg_open) {
+            int rc = fd.walk.open(ctx, dv, mp, 0, s, Family::Find, kFindGenericNonces);
+            if (rc) return rc;
+            fd.seg_open = true;
+        }
+        if (s.lo > best) {  // this segment and every later one lie above the hit
+            fd.si = fd.segs.size();
+            return HM_OK;
+        }
+        uint64_t base;
+        if (!fd.walk.peek_base(&base)) { ++fd.si; fd.seg_open = false; continue; }
+        if (base > best) {
+            // the rest of this epoch is above the hit; when its first launch
+            // already is, so is every later epoch
+            if (fd.walk.epoch_first()) fd.walk.close();
+            else fd.walk.skip_epoch();
+            continue;
+        }
+        SegStep step;
+        fd.walk.next(&step);
+        FindArgs fa;
+        fa.word = dv.find_ctl;
+        fa.tasks_run = dv.find_ctl + 1;
+        fa.target = target;
+        fa.launch_lo = step.base;
+        hipEvent_t a, b;
+        int rc = next_event(dv, &a);
+        if (rc) return rc;
+        rc = next_event(dv, &b);
+        if (rc) return rc;
+        fd.evs.push_back({a, b});
+        rc = fd.walk.launch(step, fa, a, b);
+        if (rc) return rc;
+        tally.nonces += step.nonces;
+        tally.tasks += step.ntasks;
+        ++tally.launches;
+        ++fd.inflight;
+        *issued = true;
+        return HM_OK;
+    }
+}
+
+// Wait for the device's launches in flight and read its stop word and task
+// counter back.
+int find_collect(hm_ctx* ctx, Device& dv, FindDev& fd, FindTally& tally) {
+    HIPCHK(hipSetDevice(dv.ordinal));
+    int rc = host_wait(ctx, dv.stream[0]);
+    if (rc) return rc;
+    uint64_t ctl[2];
+    rc = host_read(ctx, ctl, dv.find_ctl, sizeof ctl);
+    if (rc) return rc;
+    fd.word = ctl[0];
+    fd.run = ctl[1];
+    for (const auto& ev : fd.evs) {
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, ev.first, ev.second));
+        tally.kernel_ms += ms;
+    }
+    fd.evs.clear();
+    dv.evnext = 0;  // the events are free again
+    fd.inflight = 0;
+    return HM_OK;
+}
+
+}  // namespace
+
+// hm_find with ctx->mu held.
+int find_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
+                uint64_t target, hm_result* out, int* found) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint8_t* m;
+    size_t mlen;
+    int rc = begin_ranged_call(ctx, msg, len, lo, hi, t0, &m, &mlen);
+    if (rc) return rc;
+    const int ndev = (int)ctx->devs.size();
+    FindTally tally;
+    uint64_t best = ~0ull, run = 0;
+    if (lo <= hi && target != 0) {
+        const MsgPlan mp = plan_message(m, mlen);
+        for (auto& dv : ctx->devs) {
+            HIPCHK(hipSetDevice(dv.ordinal));
+            dv.evnext = 0;
+            // the stop word starts at MaxUint64, the task counter at 0
+            HIPCHK(hipMemsetAsync(dv.find_ctl, 0xff, sizeof(uint64_t), dv.stream[0]));
+            HIPCHK(hipMemsetAsync(dv.find_ctl + 1, 0, sizeof(uint64_t), dv.stream[0]));
+        }
+        // the per-device state dies with the call: a failure only has to
+        // drain the streams (drain_failed)
+        std::vector<FindDev> fds(ndev);
+        PieceWalk pieces(ctx, mp, lo, hi);
+        std::vector<std::vector<SegPlan>> shards;
+        // later pieces lie above a hit
+        while (best == ~0ull && pieces.next(&shards)) {
+            for (int i = 0; i < ndev; ++i) {
+                fds[i].segs = std::move(shards[i]);
+                fds[i].si = 0;
+                fds[i].seg_open = false;
+            }
+            for (;;) {
+                bool any = false;
+                for (int i = 0; i < ndev; ++i) {
+                    Device& dv = ctx->devs[i];
+                    HIPCHK(hipSetDevice(dv.ordinal));
+                    while (fds[i].inflight < kFindLookahead) {
+                        bool issued = false;
+                        rc = find_issue(ctx, dv, fds[i], mp, target, best, tally, &issued);
+                        if (rc) return drain_failed(ctx, rc);
+                        if (!issued) break;
+                    }
+                    any = any || fds[i].inflight > 0;
+                }
+                if (!any) break;
+                for (int i = 0; i < ndev; ++i) {
+                    if (!fds[i].inflight) continue;
+                    rc = find_collect(ctx, ctx->devs[i], fds[i], tally);
+                    if (rc) return drain_failed(ctx, rc);
+                    best = std::min(best, fds[i].word);
+                }
+            }
+        }
+        for (const FindDev& fd : fds) run += fd.run;
+    }
+    hm_result res{~0ull, 0};
+    int hit = 0;
+    if (lo <= hi && target != 0) {
+        // nonce MaxUint64 is the one the stop word cannot carry: tested here
+        if (best != ~0ull || (hi == ~0ull && host_hash(m, mlen, ~0ull) < target)) {
+            res.nonce = best;
+            res.hash = host_hash(m, mlen, best);
+            if (res.hash >= target || best < lo || best > hi) return HM_ERR_INTERNAL;
+            hit = 1;
+        }
+    }
+    hm_find_stats st{};
+    st.kernel_ms = tally.kernel_ms;
+    st.nonces_enqueued = tally.nonces;
+    st.tasks_total = tally.tasks;
+    st.tasks_run = run;
+    st.launches = tally.launches;
+    st.ndev = ndev;
+    st.found = hit;
+    st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
+                     .count();
+    ctx->last_find = st;
+    ctx->have_find_stats = true;
+    *out = res;
+    *found = hit;
+    return HM_OK;
+}
+
+}  // namespace hm

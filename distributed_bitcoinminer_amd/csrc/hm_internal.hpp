@@ -1,0 +1,375 @@
+// hm_internal.hpp -- what the library's host sources share: the per-device
+// state (Device), the context (hm_ctx), the constants, and the helpers each
+// file exports to the others.  Not part of the ABI (include/hipminer.h).
+//
+//   device.cpp    device and context lifetime, host_wait / host_read, K+W table growth, deadlines
+//   seg_walk.cpp  one segment -> its sequence of launches (SegWalk), the argument fillers
+//   scan.cpp      hm_scan_many: batching, the fused launch, merge, stats
+//   find.cpp      hm_find
+//   collect.cpp   hm_collect
+//   api.cpp       the extern "C" entry points and the debug exports
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <chrono>
+#include <deque>
+#include <mutex>
+#include <new>
+#include <string>
+#include <thread>
+#include <type_traits>
+#include <vector>
+
+#include "../../include/hipminer.h"
+#include "../../include/hipminer_debug.h"
+#include "kernels.hpp"
+#include "plan.hpp"
+
+namespace hm {
+
+constexpr int kStreams = 4;
+// Requests of at most this many nonces (≈3.6 ms of work) run their digit
+// segments concurrently on all streams; larger ones use the dominant-stream
+// order with tail filling (enqueue_device_batch).
+constexpr uint64_t kConcurrentNonces = 1ull << 27;
+// Workgroups per CU of a fused (small-request) launch: fewer waves per SIMD
+// than occupancy allows (6), so a task's wall time, and with it the launch's
+// tail, is about halved at < 1 % of issue rate; first tasks handed out by
+// wave slot (no opening burst of queue atomics).  Interleaved A/B over
+// flags x grids: profiles/r05/fused/fused_ab.jsonl.
+constexpr int kFusedPerCu = 3;
+constexpr uint32_t kFusedDefaultFlags = kFusedStaticFirst;
+constexpr uint32_t kFusedDefaultParts = 1;  // tiled fused tasks: one tens digit (10 steps)
+// Tasks one queue atomic fetches for a workgroup (scan_tasks.hpp lds_dequeue,
+// log2): 4, and 16 for launches of at least kBigLaunchNonces nonces
+// (HM_OPT_QUEUE_BATCH; configs[3]'s d = 12 launch: 9e11 nonces, ~24 s).
+constexpr uint32_t kQueueShift = 2;
+constexpr uint32_t kQueueShiftBig = 4;
+constexpr uint64_t kBigLaunchNonces = 100000000000ull;
+// Guided tail of a fused launch (HM_OPT_FUSED_TAIL): the tasks of the last,
+// partial wave-round are cut into up to this many pieces each.
+constexpr uint32_t kFusedDefaultTail = 2;
+// hm_find and hm_collect (find.cpp, collect.cpp)
+constexpr uint64_t kFindPieceNonces = 1ull << 40;    // per device and piece (multi-device)
+constexpr uint64_t kFindGenericNonces = 1ull << 30;  // per generic launch
+
+// No C++ exception crosses the C ABI (include/hipminer.h): the entry points
+// run their bodies through guarded(), which maps an escaping exception
+// (std::bad_alloc from the planner's vectors, anything else) to a return code.
+template <typename F>
+int guarded(F&& f) {
+    try {
+        return f();
+    } catch (const std::bad_alloc&) {
+        return HM_ERR_NOMEM;
+    } catch (...) {
+        return HM_ERR_INTERNAL;
+    }
+}
+
+struct Launch {
+    hipEvent_t start, stop;
+    uint64_t nonces;
+    int kind;
+    int grid;
+    uint32_t compressions;
+    double comp_eff;  // compressions per nonce the kernel executes (hm_stats)
+    char kernel[64];  // kernel instantiation, as rocprofv3 names it (sans args)
+};
+
+struct Device {
+    int ordinal = -1;
+    int cus = 0;
+    int prio_hi = 0, prio_lo = 0;  // stream priorities (stream 0 / streams 1..)
+    // streams (and their buffers) made so far: stream 0 at hm_open, streams
+    // 1.. on the first call that enqueues onto them (make_streams).  Each HIP
+    // stream holds a hardware queue until the process exits, and the GPU
+    // time-slices once a process set holds more than ~20, so a
+    // context that only ever runs fused requests, or HM_OPT_STREAMS = 2,
+    // never creates the others.
+    int nmade = 0;
+    hipStream_t stream[kStreams] = {};
+    uint32_t* rec[kStreams] = {};
+    uint32_t* kwt[kStreams] = {};
+    uint32_t* aux[kStreams] = {};      // fused launches: s0 / trailer / K+W tables
+    uint64_t kwt_rows[kStreams] = {};  // rows allocated (grown on demand, kw_table_rows)
+    std::vector<void*> retired;        // tables and buffers replaced by larger ones, freed at hm_close
+    uint64_t* cand[kStreams] = {};
+    unsigned int* counter[kStreams] = {};
+    uint64_t* sums[kStreams] = {};  // checked scans: per-wave (sum, count) slots
+    uint64_t* acc = nullptr;        // checked scans: [kStreams][2] (sum, count)
+    uint64_t* best = nullptr;      // [kMaxBatch][kStreams][2]: per request, per stream
+    uint64_t* result = nullptr;    // [kMaxBatch][2]
+    uint64_t* gathered = nullptr;  // [ndev][kMaxBatch][2] (RCCL merge)
+    uint64_t* find_ctl = nullptr;  // hm_find: [0] the stop word, [1] tasks run (kernels.hpp FindArgs)
+    // hm_collect: [0] total, [1] slot cursor (kernels.hpp CollectArgs), and the record buffer of
+    // collect_cap records, grown when a larger cap arrives (the old one joins `retired`)
+    uint64_t* collect_ctl = nullptr;
+    uint64_t* collect_buf = nullptr;
+    size_t collect_cap = 0;
+    hm_result* host_out = nullptr; // pinned, fine-grained [kMaxBatch]: the 16-B readback slots
+    hipEvent_t join[kStreams] = {};
+    hipEvent_t gate = nullptr;     // stream 0 reached its last dominant segment
+    hipEvent_t t0 = nullptr;       // timing origin of the current call
+    std::vector<hipEvent_t> evpool;
+    size_t evnext = 0;
+    std::vector<Launch> launches;
+    ncclComm_t comm = nullptr;
+    hipModule_t mod = nullptr;  // scan kernels (hipminer_scan.hsaco)
+    struct Fn { std::string sym; hipFunction_t fn; int blocks_per_cu; };
+    std::deque<Fn> fns;         // resolved on first use (stable addresses)
+};
+
+bool debug_on();
+int hip_fail(hipError_t e, const char* what);
+
+#define HIPCHK(expr)                                   \
+    do {                                               \
+        hipError_t e_ = (expr);                        \
+        if (e_ != hipSuccess) return hm::hip_fail(e_, #expr); \
+    } while (0)
+
+}  // namespace hm
+
+struct hm_ctx {
+    mutable std::mutex mu;
+    std::vector<hm::Device> devs;
+    bool force_generic = false;
+    bool merge_rccl = false;
+    int grid_per_cu = 0;
+    int streams = hm::kStreams;  // HM_OPT_STREAMS (tail filling by default)
+    int table_digits = 0;    // HM_OPT_TABLE_DIGITS (test hook; 0 = default, -1 = off)
+    uint64_t table_rows_cap = 0;  // HM_OPT_TABLE_ROWS_CAP (test hook; 0 = off)
+    bool test_mid_sync = false;   // HM_OPT_TEST_MID_SYNC (test hook: a host wait mid-enqueue)
+    bool fused = true;            // HM_OPT_FUSED: small requests in one launch
+    uint32_t fused_flags = hm::kFusedDefaultFlags;  // HM_OPT_FUSED_FLAGS (experiment hook)
+    uint32_t fused_parts = hm::kFusedDefaultParts;  // HM_OPT_FUSED_PARTS (experiment hook)
+    uint32_t fused_tail = hm::kFusedDefaultTail;    // HM_OPT_FUSED_TAIL (1 = no split)
+    bool tail_fused = true;  // HM_OPT_TAIL_FUSED: a large request's tail segments in one fused launch
+    int queue_batch = 0;     // HM_OPT_QUEUE_BATCH: 0 = auto, else tasks per queue atomic (4..32)
+    // host waits on GPU work while the call is still enqueuing (hm_stats.mid_call_syncs)
+    bool enqueuing = false;
+    int32_t mid_syncs = 0;
+    int32_t table_grows = 0;
+    double enqueue_ms = 0;
+    bool csum = false;  // inside hm_scan_checked: checked kernels + coverage sums
+    // HM_OPT_DEADLINE_MS: 0 = none (the host blocks until the GPU is done),
+    // > 0 = that many ms per call, -1 = auto (deadline_for).  Past the
+    // deadline a call returns HM_ERR_TIMEOUT and the context is abandoned:
+    // its queued work may still run, so no later call touches its devices
+    // and hm_close leaks them rather than wait (SURVEY §8(b) liveness).
+    int64_t deadline_opt = 0;
+    bool has_deadline = false;
+    std::chrono::steady_clock::time_point deadline_at{};
+    double deadline_ms = 0;  // the current call's deadline (hm_stats.deadline_ms)
+    bool abandoned = false;
+    bool have_stats = false;
+    int merge = HM_MERGE_NONE;  // how the current call merged device results
+    hm_stats last{};
+    bool have_find_stats = false;  // hm_find keeps its own record: `last` stays the last scan's
+    hm_find_stats last_find{};
+    bool have_collect_stats = false;  // and so does hm_collect
+    hm_collect_stats last_collect{};
+};
+
+namespace hm {
+
+// ---- device.cpp ----
+int open_devices(const int* devices, int ndev, hm_ctx** out);
+void device_free(Device& dv);
+bool distinct_ordinals(const hm_ctx* ctx);
+int next_event(Device& dv, hipEvent_t* ev);
+int make_streams(Device& dv, int n);
+int host_wait(hm_ctx* ctx, hipStream_t st);
+int host_read(hm_ctx* ctx, void* dst, const void* src, size_t n);
+int kw_table_rows(hm_ctx* ctx, Device& dv, int si, uint64_t rows);
+double modelled_deadline_ms(const hm_request* reqs, int n, bool force_generic, int table_digits,
+                            double simds);
+// Set the deadline of a call over `reqs` that began at t0 (HM_OPT_DEADLINE_MS).
+void call_deadline(hm_ctx* ctx, const hm_request* reqs, int n,
+                   std::chrono::steady_clock::time_point t0);
+
+// ---- seg_walk.cpp ----
+// Which kernels run a segment: the scan's, its checked variants, hm_find's or
+// hm_collect's.
+enum class Family { Scan, ScanCsum, Find, Collect };
+// The kernel of `family` for a segment of `kind` (s: the tiled instantiation's
+// template arguments; unused otherwise): its mangled name in
+// hipminer_scan.hsaco and the name rocprofv3 prints (sans arguments).
+struct KernelName {
+    std::string symbol, display;
+};
+KernelName kernel_name(Family family, int kind, const SegPlan* s);
+int scan_fn(Device& dv, const std::string& sym, const Device::Fn** out);
+int persistent_grid(const hm_ctx* ctx, const Device& dv, int per_cu_auto, uint64_t ntasks);
+void launch_units(const SegPlan& s, uint64_t t, uint64_t nt, uint64_t per_chunk, uint64_t step,
+                  uint32_t* unit0, uint64_t* nunits);
+uint32_t count_compressions(const SegPlan& s);
+double executed_compressions(const SegPlan& s);
+
+// Launch a scan kernel with its argument block (the kernel's only, by-value
+// parameter) on `grid` workgroups of kBlock threads.
+template <typename Args>
+int launch_scan(const Device::Fn& f, const Args& args, int grid, hipStream_t st) {
+    if (grid < 1 || (uint32_t)grid * (kBlock / kWaveSize) > kMaxCandWaves)
+        return hip_fail(hipErrorInvalidValue, "scan grid");
+    size_t size = sizeof(Args);
+    void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, const_cast<Args*>(&args),
+                   HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    HIPCHK(hipModuleLaunchKernel(f.fn, (unsigned)grid, 1, 1, kBlock, 1, 1, 0, st, nullptr, cfg));
+    return HM_OK;
+}
+
+// One launch of a segment, as SegWalk::next yields it.
+struct SegStep {
+    int kind;        // HM_KIND_*: which of t, c, g is filled (cand and sums null)
+    TiledArgs t;
+    ChainedArgs c;
+    GenericArgs g;
+    // the launch's smallest nonce (a wrap past 2^64 in a segment's last tile
+    // only makes it look lower: to hm_find a launch more, never one less)
+    uint64_t base;
+    uint64_t nonces;  // chained: the epoch's share of the tiles' nonces (an estimate)
+    uint64_t nunits;  // work units kept (launch_units)
+    uint32_t ntasks;  // tasks (generic: wave steps of 64 nonces)
+    int grid;
+    // what the stream-side prologue needs
+    uint64_t tile, ntiles, epoch;
+    uint32_t unit0;
+};
+// What follows a step's argument block in the kernel's parameter: nothing
+// (scan), FindArgs or CollectArgs -- the layout of kernels.hpp's Find*Args and
+// Collect*Args.
+struct NoTrailer {};
+template <typename Base, typename Trailer>
+struct WithTrailer {
+    Base b;
+    Trailer t;
+};
+static_assert(sizeof(WithTrailer<TiledArgs, FindArgs>) == sizeof(FindTiledArgs) &&
+              sizeof(WithTrailer<ChainedArgs, FindArgs>) == sizeof(FindChainedArgs) &&
+              sizeof(WithTrailer<GenericArgs, FindArgs>) == sizeof(FindGenericArgs) &&
+              sizeof(WithTrailer<TiledArgs, CollectArgs>) == sizeof(CollectTiledArgs) &&
+              sizeof(WithTrailer<ChainedArgs, CollectArgs>) == sizeof(CollectChainedArgs) &&
+              sizeof(WithTrailer<GenericArgs, CollectArgs>) == sizeof(CollectGenericArgs));
+
+// A resumable cursor over the launches of one segment on one device and
+// stream.  Generic segments run in chunks of `generic_chunk` nonces; tiled ones
+// in windows of at most max_launch_tiles tiles; chained ones in epochs (one
+// K+W table each) of such windows: epoch-major, then ascending tiles.  next()
+// only plans a launch; launch() puts it, after its prologue, on the stream.
+struct SegWalk {
+    // Start on segment seg; generic_chunk = 0: the whole segment in one launch.
+    // A chained segment gets its table here (chained_table: on a device short
+    // of memory the walk's private copy of the plan has more, smaller epochs).
+    int open(hm_ctx* ctx, Device& dv, const MsgPlan& mp, int si, const SegPlan& seg, Family family,
+             uint64_t generic_chunk);
+    // The next launch, advancing past it; false: none left.
+    bool next(SegStep* step);
+    // hm_find's pruning: the next launch's `base` without advancing (false:
+    // none left); whether that launch is its epoch's first; drop the rest of
+    // the epoch, or of the segment.
+    bool peek_base(uint64_t* base) const;
+    bool epoch_first() const { return s.kind != HM_KIND_GENERIC && t == s.tile_lo; }
+    void skip_epoch() { ++e; t = s.tile_lo; }
+    void close() { e = nep; }
+    // Enqueue a step: its prologue (K+W table when the epoch on the stream
+    // changes, tile records, queue-counter reset), then the family's kernel
+    // with the step's argument block followed by `trailer`, between the events
+    // `start` and `stop` (either may be null: not recorded).
+    template <typename Trailer>
+    int launch(const SegStep& step, const Trailer& trailer, hipEvent_t start, hipEvent_t stop);
+
+    SegPlan s;        // the segment as it runs
+    KernelName name;  // the kernel that runs it
+
+private:
+    int prologue(const SegStep& step);
+    template <typename Base, typename Trailer>
+    int launch_args(const Base& base, const Trailer& trailer, const SegStep& step,
+                    hipEvent_t start, hipEvent_t stop);
+
+    hm_ctx* ctx = nullptr;
+    Device* dv = nullptr;
+    const MsgPlan* mp = nullptr;
+    const Device::Fn* fn = nullptr;
+    int si = 0;
+    uint64_t chunk_m1 = 0;     // generic: nonces per launch - 1
+    uint64_t nep = 0;          // epochs (1 unless chained); e == nep: no launch left
+    uint64_t nloop = 0;        // chained: table rows = loop values per lane and epoch
+    uint64_t max_tiles = 0;
+    uint32_t kw[64] = {};      // the trailer block's K+W (zeros without a trailer)
+    uint64_t e = 0, t = 0, g = 0;    // cursor: epoch, tile, generic nonce
+    uint64_t table_epoch = ~0ull;    // chained: epoch of the K+W table on the stream
+};
+
+template <typename Base, typename Trailer>
+int SegWalk::launch_args(const Base& base, const Trailer& trailer, const SegStep& step,
+                         hipEvent_t start, hipEvent_t stop) {
+    hipStream_t st = dv->stream[si];
+    int rc = prologue(step);
+    if (rc) return rc;
+    if (start) HIPCHK(hipEventRecord(start, st));
+    if constexpr (std::is_same_v<Trailer, NoTrailer>) {
+        rc = launch_scan(*fn, base, step.grid, st);
+    } else {
+        rc = launch_scan(*fn, WithTrailer<Base, Trailer>{base, trailer}, step.grid, st);
+    }
+    if (rc) return rc;
+    if (stop) HIPCHK(hipEventRecord(stop, st));
+    return HM_OK;
+}
+
+template <typename Trailer>
+int SegWalk::launch(const SegStep& step, const Trailer& trailer, hipEvent_t start,
+                    hipEvent_t stop) {
+    switch (step.kind) {
+        case HM_KIND_TILED: return launch_args(step.t, trailer, step, start, stop);
+        case HM_KIND_CHAINED: return launch_args(step.c, trailer, step, start, stop);
+        default: return launch_args(step.g, trailer, step, start, stop);
+    }
+}
+
+// The pieces hm_find and hm_collect cut [lo, hi] into, in ascending order:
+// each digit segment is one piece; with several devices, pieces of at most
+// kFindPieceNonces per device, cut at tile boundaries and split across the
+// devices with partition_range.
+struct PieceWalk {
+    PieceWalk(const hm_ctx* ctx, const MsgPlan& mp, uint64_t lo, uint64_t hi);
+    // The next piece: (*shards)[i] = device i's segments (none: no share of
+    // this piece).  false: no piece left.
+    bool next(std::vector<std::vector<SegPlan>>* shards);
+
+private:
+    const hm_ctx* ctx;
+    const MsgPlan& mp;
+    std::vector<SegPlan> segs;
+    size_t i = 0;
+    uint64_t a = 0;  // the next piece's first nonce
+};
+
+// The opening of an hm_find or hm_collect call that began at t0: a null
+// message is the empty one (*m, *mlen), the call's deadline is set; refuses an
+// abandoned context.
+int begin_ranged_call(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
+                      std::chrono::steady_clock::time_point t0, const uint8_t** m, size_t* mlen);
+// A find or collect that fails part-way with rc leaves nothing behind: every
+// device's stream 0 is waited for (launches still queued use its record,
+// table, counter and control buffers) and its timing events are free again.
+// After a timeout the context is abandoned and nothing is waited for, as for
+// a scan.  Returns rc.
+int drain_failed(hm_ctx* ctx, int rc);
+
+// ---- scan.cpp, find.cpp, collect.cpp: the entry points' bodies, ctx->mu held ----
+int scan_many_locked(hm_ctx* ctx, const hm_request* reqs, int n, hm_result* outs);
+int find_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
+                uint64_t target, hm_result* out, int* found);
+int collect_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
+                   uint64_t target, size_t cap, std::vector<hm_result>* recs, uint64_t* total);
+
+}  // namespace hm

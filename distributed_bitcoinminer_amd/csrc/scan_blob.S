@@ -1,6 +1,6 @@
 /* scan_blob.S -- embeds the scan kernels' code object (hipminer_scan.hsaco,
  * built from scan_kernels.hip by the Makefile: hipcc -S, align_loops.py,
- * clang -x assembler, ld.lld) into libhipminer.so; api.cpp loads it per
+ * clang -x assembler, ld.lld) into libhipminer.so; device.cpp loads it per
  * device with hipModuleLoadData. */
     .section .rodata.hm_scan_code_object, "a", @progbits
     .globl hm_scan_code_object

@@ -3,7 +3,7 @@
 Lanes vary the last q digits of tail block 0, the final block's low fe digits
 come from a K+W table (10^fe rows) and its high f - fe digits run as epochs,
 one table and launch set each (plan.cpp consider_chained_epochs,
-api.cpp enqueue_chained).  Every case goes through hm_scan_checked and is
+scan.cpp enqueue_segment over seg_walk.cpp SegWalk).  Every case goes through hm_scan_checked and is
 compared with the SHA-extension CPU oracle's (min, key sum, count)
 (oracle/hm_oracle_fast.c, itself checked against oracle/hm_oracle.c), so a
 skipped, doubled or mis-hashed nonce fails.  The reference loop is

@@ -1,7 +1,7 @@
 """The host never waits on the GPU while a call is still enqueuing (ABI 1.6).
 
 Chained f >= 5 segments grow their stream's K+W table (10^5 .. 10^7 rows).
-Work queued earlier may still read the old table, so it is retired (api.cpp
+Work queued earlier may still read the old table, so it is retired (device.cpp
 kw_table_rows; freed at hm_close -- ABI 1.7 freed it at the end of the call,
 but hipFree waits for the whole device, other contexts' work included)
 instead of freed, which would drain the device mid-enqueue: every device of a
@@ -87,7 +87,7 @@ def test_single_device_growth_on_second_stream(oracle_mod):
 def test_table_rows_cap_falls_back_to_epochs(oracle_mod, cap, req, f):
     """HM_OPT_TABLE_ROWS_CAP makes table growth fail as on a device out of
     memory: the chained layout falls back to a table of 10^(f-1) rows and 10
-    epochs (enqueue_chained), and the answer and checksum are unchanged."""
+    epochs (seg_walk.cpp chained_table), and the answer and checksum are unchanged."""
     m, lo, hi = req
     exp = oracle_mod.fast_scan_sum(m, lo, hi, threads=THREADS)
     with _lib.Context([0]) as c:

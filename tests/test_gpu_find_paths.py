@@ -178,7 +178,7 @@ PIECE_HALF = 70_000
 
 
 def _piece_boundary(m, ndev, generic):
-    """The first multiple of the multi-device piece span, as find_locked
+    """The first multiple of the multi-device piece span, as PieceWalk
     computes it: ndev * 2^40 nonces, rounded down to whole tiles of 10^V
     where the segment is not generic."""
     span = ndev << 40
@@ -313,7 +313,7 @@ OPEN_TABLE_DIGITS = 4  # hm_open makes every stream a K+W table of 10^4 rows
 
 def test_table_rows_cap_mid_call(oracle_mod):
     """A device that refuses to grow its K+W table beyond 10^4, then 10^2,
-    rows: the segment is planned with fe = 5 (10^5 rows), find_open_seg's
+    rows: the segment is planned with fe = 5 (10^5 rows), SegWalk::open's
     chained_table shrinks it mid-call to the largest table the device has or
     may make -- 10^4 rows under either cap, the table hm_open made -- and the
     find runs 10^(5 - fe) epochs over the same tiles.  (Tables below 10^4

@@ -139,7 +139,7 @@ def test_generic_vs_tiled_large(ctx):
 def test_options_streams_and_rccl_merge(oracle_mod):
     """Multi-stream segment overlap and the in-library RCCL merge of the 16-B
     per-device results (ncclCommInitAll + grouped ncclAllGather + the strided
-    device-side fold over the gathered candidates, api.cpp rccl_merge) give
+    device-side fold over the gathered candidates, scan.cpp rccl_merge) give
     the same answers as the oracle.  On this 1-GPU box the communicator has
     one rank; the merge path is the one an 8-device context takes, and
     hm_stats.merge records that it ran (server.go:273-276 merge semantics)."""
@@ -189,7 +189,7 @@ def test_rccl_merge_distinct_devices(oracle_mod):
     """The in-library RCCL merge over DISTINCT device ordinals: ncclCommInitAll
     over every visible GPU, one rank per device, each scanning its
     hm_partition shard, then the grouped ncclAllGather of the 16-B results and
-    the device-side fold (api.cpp rccl_merge; the multi-device form of
+    the device-side fold (scan.cpp rccl_merge; the multi-device form of
     server.go:273-276).  Needs >= 2 GPUs: the 1-GPU box skips it."""
     import torch
     n = torch.cuda.device_count()
