@@ -39,6 +39,7 @@ HM_OPT_DEADLINE_MS = 13
 HM_OPT_FUSED_TAIL = 14
 HM_OPT_TAIL_FUSED = 15
 HM_OPT_QUEUE_BATCH = 17
+HM_OPT_VERIFY_CHUNK = 19
 HM_MERGE_NONE, HM_MERGE_HOST, HM_MERGE_RCCL = 0, 1, 2
 
 
@@ -98,7 +99,20 @@ class hm_collect_stats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class hm_verify_stats(ctypes.Structure):
+    """hm_verify_stats of include/hipminer.h (ABI 1.12)."""
+    _fields_ = [("wall_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
+                ("copy_ms", ctypes.c_double), ("records", ctypes.c_uint64),
+                ("bad", ctypes.c_uint64), ("launches", ctypes.c_int32),
+                ("ndev", ctypes.c_int32), ("overflow", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 HM_COLLECT_CAP_MAX = 1 << 24
+HM_VERIFY_CAP_MAX = 1 << 20
 
 _lib = None
 _lock = threading.Lock()
@@ -180,6 +194,23 @@ def load() -> ctypes.CDLL:
         lib.hm_collect_stats_sized.restype = ctypes.c_int
         lib.hm_collect_stats_sized.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_collect_stats),
                                                ctypes.c_size_t]
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        lib.hm_hash_many.restype = ctypes.c_int
+        lib.hm_hash_many.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, u64p, ctypes.c_size_t,
+                                     u64p]
+        lib.hm_hash_many_cpu.restype = ctypes.c_int
+        lib.hm_hash_many_cpu.argtypes = [u8p, ctypes.c_size_t, u64p, ctypes.c_size_t, ctypes.c_int,
+                                         u64p]
+        lib.hm_verify.restype = ctypes.c_int
+        lib.hm_verify.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.POINTER(hm_result),
+                                  ctypes.c_size_t, ctypes.c_uint64, u64p, ctypes.c_size_t, u64p]
+        lib.hm_verify_cpu.restype = ctypes.c_int
+        lib.hm_verify_cpu.argtypes = [u8p, ctypes.c_size_t, ctypes.POINTER(hm_result),
+                                      ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int, u64p,
+                                      ctypes.c_size_t, u64p]
+        lib.hm_verify_stats_sized.restype = ctypes.c_int
+        lib.hm_verify_stats_sized.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_verify_stats),
+                                              ctypes.c_size_t]
         lib.hm_debug_auto_deadline_ms.restype = ctypes.c_double
         lib.hm_debug_auto_deadline_ms.argtypes = [u8p, ctypes.c_size_t, ctypes.c_uint64,
                                                   ctypes.c_uint64, ctypes.c_int]
@@ -305,6 +336,30 @@ class Context:
             raise HipMinerError(rc, "hm_collect_stats_sized")
         return st.as_dict()
 
+    def hash_many(self, msg, nonces):
+        """hm_hash_many (ABI 1.12): numpy.uint64 array of Hash(msg, n) for each
+        n of `nonces` (a numpy.uint64 array or a sequence of ints), any order,
+        any digit counts."""
+        return _hash_many(lambda m, a, n, o: self._lib.hm_hash_many(self._h, m, len(m), a, n, o),
+                          "hm_hash_many", msg, nonces)
+
+    def verify(self, msg, records, target: int, cap: int):
+        """hm_verify (ABI 1.12): (bad, indices).  A record (hash, nonce) is bad
+        when hash != Hash(msg, nonce) or hash >= target.  bad = their number,
+        always exact; indices = numpy.uint64 array of their positions,
+        ascending, when bad <= cap, and None when bad > cap.  `records` is an
+        (n, 2) numpy.uint64 array or a list of (hash, nonce) pairs."""
+        return _verify(lambda m, r, n, idx, c, bad: self._lib.hm_verify(
+            self._h, m, len(m), r, n, target, idx, c, bad), "hm_verify", msg, records, cap)
+
+    def verify_stats(self) -> dict:
+        """hm_verify_stats_sized: accounting of the last hash_many or verify."""
+        st = hm_verify_stats()
+        rc = self._lib.hm_verify_stats_sized(self._h, ctypes.byref(st), ctypes.sizeof(st))
+        if rc != HM_OK:
+            raise HipMinerError(rc, "hm_verify_stats_sized")
+        return st.as_dict()
+
     def streams_made(self, device_index: int = 0) -> int:
         """HIP streams (hardware queues) the context has made on its
         device_index-th device (debug export; ABI 1.8 makes them on first use)."""
@@ -390,6 +445,47 @@ def collect_cpu(msg, lo: int, hi: int, target: int, cap: int, threads: int = 0):
 def count_cpu(msg, lo: int, hi: int, target: int, threads: int = 0) -> int:
     """hm_collect_cpu with no buffer: Context.count's answer on the host's cores."""
     return collect_cpu(msg, lo, hi, target, 0, threads)[0]
+
+
+def _hash_many(call, what: str, msg, nonces):
+    import numpy as np
+    m = as_bytes(msg)
+    a = np.ascontiguousarray(nonces, dtype=np.uint64).reshape(-1)
+    out = np.empty(a.size, dtype=np.uint64)
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    rc = call(m, a.ctypes.data_as(u64p) if a.size else None, a.size,
+              out.ctypes.data_as(u64p) if a.size else None)
+    if rc != HM_OK:
+        raise HipMinerError(rc, what)
+    return out
+
+
+def _verify(call, what: str, msg, records, cap: int):
+    import numpy as np
+    m = as_bytes(msg)
+    r = np.ascontiguousarray(records, dtype=np.uint64).reshape(-1, 2)
+    n = r.shape[0]
+    idx = np.empty(cap, dtype=np.uint64) if cap else None
+    bad = ctypes.c_uint64(0)
+    rc = call(m, r.ctypes.data_as(ctypes.POINTER(hm_result)) if n else None, n,
+              idx.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if cap else None, cap,
+              ctypes.byref(bad))
+    if rc != HM_OK:
+        raise HipMinerError(rc, what)
+    b = int(bad.value)
+    return (b, None) if b > cap else (b, idx[:b].copy() if cap else np.empty(0, np.uint64))
+
+
+def hash_many_cpu(msg, nonces, threads: int = 0):
+    """hm_hash_many_cpu (ABI 1.12): Context.hash_many's answer on the host's cores."""
+    return _hash_many(lambda m, a, n, o: load().hm_hash_many_cpu(m, len(m), a, n, threads, o),
+                      "hm_hash_many_cpu", msg, nonces)
+
+
+def verify_cpu(msg, records, target: int, cap: int, threads: int = 0):
+    """hm_verify_cpu (ABI 1.12): Context.verify's answer on the host's cores."""
+    return _verify(lambda m, r, n, idx, c, bad: load().hm_verify_cpu(
+        m, len(m), r, n, target, threads, idx, c, bad), "hm_verify_cpu", msg, records, cap)
 
 
 def partition(msg, lo: int, hi: int, n: int) -> list:

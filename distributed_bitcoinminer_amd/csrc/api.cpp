@@ -18,6 +18,8 @@
 //   find_kernels.hip.  hm_collect (ABI 1.11): collect.cpp, the kernels of
 //   collect_kernels.hip.  All three walk a segment's launches with SegWalk
 //   (seg_walk.cpp); devices, streams and host waits are device.cpp's.
+//   hm_hash_many and hm_verify (ABI 1.12): verify.cpp, a list of arbitrary
+//   nonces through the one kernel of verify_kernels.hip.
 //   The scan kernels come from their own code object (scan_kernels.hip ->
 //   align_loops.py -> hipminer_scan.hsaco, embedded by scan_blob.S), loaded
 //   per device with hipModuleLoadData and launched with hipModuleLaunchKernel.
@@ -49,7 +51,8 @@ uint64_t hm_hash(const uint8_t* msg, size_t len, uint64_t nonce) {
 //      test and experiment hooks and hm_debug_* prototypes moved to hipminer_debug.h
 // 1.10: hm_find, hm_find_cpu, hm_find_stats_sized
 // 1.11: hm_collect, hm_collect_cpu, hm_collect_stats_sized
-int hm_version(void) { return (1 << 16) | 11; }
+// 1.12: hm_hash_many, hm_hash_many_cpu, hm_verify, hm_verify_cpu, hm_verify_stats_sized
+int hm_version(void) { return (1 << 16) | 12; }
 
 // The digest of the sources this library was built from (build_id.py), kept
 // in the binary behind a tag so tools can read it without loading the library.
@@ -160,6 +163,11 @@ int hm_set_option(hm_ctx* ctx, int opt, int64_t value) {
             if (value != 1 && value != 2 && value != 5 && value != 10) return HM_ERR_INVALID;
             ctx->fused_tail = (uint32_t)value;
             return HM_OK;
+        case HM_OPT_VERIFY_CHUNK:
+            if (value < 0 || value > (int64_t)kVerifyChunk || value % kWaveSize != 0)
+                return HM_ERR_INVALID;
+            ctx->verify_chunk = (uint32_t)value;
+            return HM_OK;
         case HM_OPT_GRID_PER_CU:
             if (value < 0 || value > 32) return HM_ERR_INVALID;
             ctx->grid_per_cu = (int)value;
@@ -250,6 +258,45 @@ int hm_collect_stats_sized(const hm_ctx* ctx, hm_collect_stats* out, size_t size
     std::lock_guard<std::mutex> g(ctx->mu);
     if (!ctx->have_collect_stats) return HM_ERR_INVALID;
     memcpy(out, &ctx->last_collect, std::min(size, sizeof(hm_collect_stats)));
+    return HM_OK;
+}
+
+int hm_hash_many(hm_ctx* ctx, const uint8_t* msg, size_t len, const uint64_t* nonces, size_t n,
+                 uint64_t* hashes) {
+    if (!ctx || (!msg && len) || (n && (!nonces || !hashes))) return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    std::vector<uint64_t> out;
+    uint64_t bad = 0;
+    int rc = guarded(
+        [&] { return list_locked(ctx, msg, len, nonces, nullptr, n, 0, 0, &out, &bad); });
+    if (rc) return rc;
+    // all n hashes, or (on any failure above) nothing
+    if (n) memcpy(hashes, out.data(), n * sizeof(uint64_t));
+    return HM_OK;
+}
+
+int hm_verify(hm_ctx* ctx, const uint8_t* msg, size_t len, const hm_result* recs, size_t n,
+              uint64_t target, uint64_t* bad_idx, size_t cap, uint64_t* bad) {
+    if (!ctx || !bad || (!msg && len) || (n && !recs) || cap > HM_VERIFY_CAP_MAX ||
+        (cap && !bad_idx))
+        return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    std::vector<uint64_t> idx;
+    uint64_t sum = 0;
+    int rc = guarded(
+        [&] { return list_locked(ctx, msg, len, nullptr, recs, n, target, cap, &idx, &sum); });
+    if (rc) return rc;
+    // sum > cap: bad_idx is not written at all
+    if (sum <= cap && sum) memcpy(bad_idx, idx.data(), (size_t)sum * sizeof(uint64_t));
+    *bad = sum;
+    return HM_OK;
+}
+
+int hm_verify_stats_sized(const hm_ctx* ctx, hm_verify_stats* out, size_t size) {
+    if (!ctx || !out || size < HM_VERIFY_STATS_SIZE_1_12) return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!ctx->have_verify_stats) return HM_ERR_INVALID;
+    memcpy(out, &ctx->last_verify, std::min(size, sizeof(hm_verify_stats)));
     return HM_OK;
 }
 

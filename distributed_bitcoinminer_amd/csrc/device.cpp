@@ -105,6 +105,9 @@ void device_free(Device& dv) {
     if (dv.find_ctl) (void)hipFree(dv.find_ctl);
     if (dv.collect_ctl) (void)hipFree(dv.collect_ctl);
     if (dv.collect_buf) (void)hipFree(dv.collect_buf);
+    if (dv.verify_ctl) (void)hipFree(dv.verify_ctl);
+    if (dv.verify_in) (void)hipFree(dv.verify_in);
+    if (dv.verify_idx) (void)hipFree(dv.verify_idx);
     if (dv.host_out) (void)hipHostFree(dv.host_out);
     dv.ordinal = -1;
 }
@@ -256,15 +259,30 @@ static double auto_deadline_ms(const hm_ctx* ctx, const hm_request* reqs, int n)
                                 4.0 * ctx->devs[0].cus * (double)ords.size());
 }
 
-void call_deadline(hm_ctx* ctx, const hm_request* reqs, int n,
-                   std::chrono::steady_clock::time_point t0) {
+static void set_deadline(hm_ctx* ctx, double auto_ms, std::chrono::steady_clock::time_point t0) {
     ctx->has_deadline = ctx->deadline_opt != 0;
     ctx->deadline_ms = !ctx->has_deadline ? 0.0
                        : ctx->deadline_opt > 0 ? (double)ctx->deadline_opt
-                                               : auto_deadline_ms(ctx, reqs, n);
+                                               : auto_ms;
     if (ctx->has_deadline)
         ctx->deadline_at = t0 + std::chrono::duration_cast<std::chrono::steady_clock::duration>(
                                     std::chrono::duration<double, std::milli>(ctx->deadline_ms));
+}
+
+void call_deadline(hm_ctx* ctx, const hm_request* reqs, int n,
+                   std::chrono::steady_clock::time_point t0) {
+    set_deadline(ctx, ctx->deadline_opt < 0 ? auto_deadline_ms(ctx, reqs, n) : 0.0, t0);
+}
+
+// hm_hash_many and hm_verify have no range to model: auto is the same floor
+// plus the same slack times a wall time per list element: the median wall of
+// hm_verify over 4,192,403 records of the 120-B message, the slower of the two
+// messages measured (1.6845 ms; profiles/verify/verify_rate.jsonl part (a)).
+constexpr double kVerifyNsPerRecord = 0.402;
+
+void list_deadline(hm_ctx* ctx, size_t n, std::chrono::steady_clock::time_point t0) {
+    set_deadline(ctx, kDeadlineFloorMs + kDeadlineSlack * kVerifyNsPerRecord * 1e-6 * (double)n,
+                 t0);
 }
 
 }  // namespace hm

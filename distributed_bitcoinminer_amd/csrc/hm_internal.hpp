@@ -7,6 +7,7 @@
 //   scan.cpp      hm_scan_many: batching, the fused launch, merge, stats
 //   find.cpp      hm_find
 //   collect.cpp   hm_collect
+//   verify.cpp    hm_hash_many, hm_verify
 //   api.cpp       the extern "C" entry points and the debug exports
 #pragma once
 #include <hip/hip_runtime.h>
@@ -57,6 +58,9 @@ constexpr uint32_t kFusedDefaultTail = 2;
 // hm_find and hm_collect (find.cpp, collect.cpp)
 constexpr uint64_t kFindPieceNonces = 1ull << 40;    // per device and piece (multi-device)
 constexpr uint64_t kFindGenericNonces = 1ull << 30;  // per generic launch
+// hm_hash_many and hm_verify (verify.cpp): list elements per chunk and device
+// (one copy in, one launch; HM_OPT_VERIFY_CHUNK)
+constexpr uint32_t kVerifyChunk = 1u << 22;
 
 // No C++ exception crosses the C ABI (include/hipminer.h): the entry points
 // run their bodies through guarded(), which maps an escaping exception
@@ -112,6 +116,14 @@ struct Device {
     uint64_t* collect_ctl = nullptr;
     uint64_t* collect_buf = nullptr;
     size_t collect_cap = 0;
+    // hm_hash_many / hm_verify, all made on first use: [0] total, [1] slot cursor (kernels.hpp
+    // VerifyArgs); the chunk buffer of verify_in_bytes bytes (nonces, or 16-byte records) and the
+    // index buffer of verify_idx_cap indices, grown like collect_buf
+    uint64_t* verify_ctl = nullptr;
+    uint64_t* verify_in = nullptr;
+    size_t verify_in_bytes = 0;
+    uint64_t* verify_idx = nullptr;
+    size_t verify_idx_cap = 0;
     hm_result* host_out = nullptr; // pinned, fine-grained [kMaxBatch]: the 16-B readback slots
     hipEvent_t join[kStreams] = {};
     hipEvent_t gate = nullptr;     // stream 0 reached its last dominant segment
@@ -152,6 +164,7 @@ struct hm_ctx {
     uint32_t fused_tail = hm::kFusedDefaultTail;    // HM_OPT_FUSED_TAIL (1 = no split)
     bool tail_fused = true;  // HM_OPT_TAIL_FUSED: a large request's tail segments in one fused launch
     int queue_batch = 0;     // HM_OPT_QUEUE_BATCH: 0 = auto, else tasks per queue atomic (4..32)
+    uint32_t verify_chunk = 0;  // HM_OPT_VERIFY_CHUNK (test hook; 0 = kVerifyChunk)
     // host waits on GPU work while the call is still enqueuing (hm_stats.mid_call_syncs)
     bool enqueuing = false;
     int32_t mid_syncs = 0;
@@ -175,6 +188,8 @@ struct hm_ctx {
     hm_find_stats last_find{};
     bool have_collect_stats = false;  // and so does hm_collect
     hm_collect_stats last_collect{};
+    bool have_verify_stats = false;  // and hm_hash_many / hm_verify
+    hm_verify_stats last_verify{};
 };
 
 namespace hm {
@@ -193,6 +208,8 @@ double modelled_deadline_ms(const hm_request* reqs, int n, bool force_generic, i
 // Set the deadline of a call over `reqs` that began at t0 (HM_OPT_DEADLINE_MS).
 void call_deadline(hm_ctx* ctx, const hm_request* reqs, int n,
                    std::chrono::steady_clock::time_point t0);
+// Set the deadline of an hm_hash_many or hm_verify call over n list elements.
+void list_deadline(hm_ctx* ctx, size_t n, std::chrono::steady_clock::time_point t0);
 
 // ---- seg_walk.cpp ----
 // Which kernels run a segment: the scan's, its checked variants, hm_find's or
@@ -358,18 +375,24 @@ private:
 // abandoned context.
 int begin_ranged_call(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
                       std::chrono::steady_clock::time_point t0, const uint8_t** m, size_t* mlen);
-// A find or collect that fails part-way with rc leaves nothing behind: every
+// A find, collect, hash_many or verify that fails part-way with rc leaves nothing behind: every
 // device's stream 0 is waited for (launches still queued use its record,
 // table, counter and control buffers) and its timing events are free again.
 // After a timeout the context is abandoned and nothing is waited for, as for
 // a scan.  Returns rc.
 int drain_failed(hm_ctx* ctx, int rc);
 
-// ---- scan.cpp, find.cpp, collect.cpp: the entry points' bodies, ctx->mu held ----
+// ---- scan.cpp, find.cpp, collect.cpp, verify.cpp: the entry points' bodies, ctx->mu held ----
 int scan_many_locked(hm_ctx* ctx, const hm_request* reqs, int n, hm_result* outs);
 int find_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
                 uint64_t target, hm_result* out, int* found);
 int collect_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
                    uint64_t target, size_t cap, std::vector<hm_result>* recs, uint64_t* total);
+// hm_hash_many (recs null: `list` holds n nonces, *out gets the n hashes) and
+// hm_verify (recs: n records; *out gets the bad indices, ascending, when
+// *bad <= cap and stays empty otherwise).
+int list_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, const uint64_t* nonces,
+                const hm_result* recs, size_t n, uint64_t target, size_t cap,
+                std::vector<uint64_t>* out, uint64_t* bad);
 
 }  // namespace hm

@@ -1,6 +1,7 @@
-// host_scan.cpp -- hm_scan_cpu, hm_find_cpu and hm_collect_cpu: the min-hash
-// scan, the first-below-target search (ABI 1.10) and the all-below-target
-// collection (ABI 1.11), on the host's cores.
+// host_scan.cpp -- hm_scan_cpu, hm_find_cpu, hm_collect_cpu, hm_hash_many_cpu
+// and hm_verify_cpu: the min-hash scan, the first-below-target search (ABI
+// 1.10), the all-below-target collection (ABI 1.11) and the recheck of a list
+// (ABI 1.12), on the host's cores.
 //
 // SURVEY §8(b)'s liveness path.  The reference miner always answers a
 // Request with a Result (cmu440/bitcoin/miner/miner.go:60-62); a GPU miner
@@ -229,6 +230,57 @@ void collect_chunk(const MsgPlan& mp, uint64_t a, uint64_t b, uint64_t target, s
     }
 }
 
+// Hash(msg, n) of one nonce from the midstate: the tail bytes of walk_chunk,
+// built for n alone, and one or two compressions.
+uint64_t hash_from_mid(const MsgPlan& mp, uint64_t n, CompressFn compress) {
+    const uint32_t r = mp.r, d = digits_u64(n);
+    uint8_t tail[128];
+    memset(tail, 0, sizeof tail);
+    for (uint32_t i = 0; i < r; ++i) tail[i] = (uint8_t)(mp.pw[i / 4] >> (24 - 8 * (i % 4)));
+    uint64_t x = n;
+    for (uint32_t k = 0; k < d; ++k) {
+        tail[r + d - 1 - k] = (uint8_t)('0' + x % 10);
+        x /= 10;
+    }
+    const uint32_t T = r + d;
+    tail[T] = 0x80;
+    const uint32_t nb = T + 9 <= 64 ? 1 : 2;
+    const uint64_t bits = (mp.len + 1 + d) * 8;
+    for (int i = 0; i < 8; ++i) tail[64 * nb - 1 - i] = (uint8_t)(bits >> (8 * i));
+    uint32_t s[8], o[8];
+    if (nb == 2) compress(mp.mid, tail, s);
+    else memcpy(s, mp.mid, sizeof s);
+    compress(s, tail + 64 * (nb - 1), o);
+    return ((uint64_t)o[0] << 32) | o[1];
+}
+
+// hm_verify_cpu's share of one thread: the bad indices of its contiguous part
+// of the list, ascending, and their count; like CollectPart, it stops storing
+// once the part alone holds more than `cap` and keeps counting.
+struct VerifyPart {
+    std::vector<uint64_t> idx;
+    uint64_t count = 0;
+    bool failed = false;  // out of memory
+};
+
+void hash_part(const MsgPlan& mp, const uint64_t* nonces, size_t a, size_t b, CompressFn compress,
+               uint64_t* hashes) {
+    for (size_t i = a; i < b; ++i) hashes[i] = hash_from_mid(mp, nonces[i], compress);
+}
+
+void verify_part(const MsgPlan& mp, const hm_result* recs, size_t a, size_t b, uint64_t target,
+                 size_t cap, CompressFn compress, VerifyPart* out) {
+    try {
+        for (size_t i = a; i < b; ++i) {
+            const bool bad = recs[i].hash >= target ||
+                             recs[i].hash != hash_from_mid(mp, recs[i].nonce, compress);
+            if (bad && ++out->count <= cap) out->idx.push_back(i);
+        }
+    } catch (...) {
+        out->failed = true;
+    }
+}
+
 // Default thread count: the CPUs this process may run on.  A GPU box's
 // per-GPU share is an affinity set inside a machine whose
 // hardware_concurrency() counts every CPU, many times more.
@@ -239,6 +291,39 @@ unsigned default_threads() {
         if (c > 0) return (unsigned)c;
     }
     return std::max(1u, std::thread::hardware_concurrency());
+}
+
+// Run work(t, a, b) over [0, n) cut into contiguous, near-equal parts, one
+// thread each (the last part on the calling thread); lists below 1024
+// elements per thread use fewer.  prepare(parts) runs first, so the caller
+// can size its per-part state.
+template <typename Prepare, typename Work>
+int over_list(size_t n, int threads, Prepare&& prepare, Work&& work) {
+    unsigned nt = threads > 0 ? (unsigned)threads : default_threads();
+    nt = std::min(nt, 1024u);
+    if (n < (size_t)nt * 1024) nt = (unsigned)std::max<size_t>(1, n / 1024);
+    prepare(nt);
+    std::vector<std::thread> pool;
+    pool.reserve(nt);
+    const size_t per = n / nt, extra = n % nt;
+    size_t start = 0;
+    int rc = HM_OK;
+    for (unsigned t = 0; t < nt; ++t) {
+        const size_t a = start, b = start + per + (t < extra ? 1 : 0);
+        start = b;
+        if (t + 1 == nt) {
+            work(t, a, b);  // the calling thread
+            break;
+        }
+        try {
+            pool.emplace_back(work, t, a, b);
+        } catch (...) {  // no thread: join the started ones before failing
+            rc = HM_ERR_INTERNAL;
+            break;
+        }
+    }
+    for (auto& th : pool) th.join();
+    return rc;
 }
 
 }  // namespace
@@ -400,6 +485,74 @@ extern "C" int hm_collect_cpu(const uint8_t* msg, size_t len, uint64_t lo, uint6
             }
         }
         *total = sum;
+        return HM_OK;
+    } catch (const std::bad_alloc&) {
+        return HM_ERR_NOMEM;
+    } catch (...) {
+        return HM_ERR_INTERNAL;
+    }
+}
+
+extern "C" int hm_hash_many_cpu(const uint8_t* msg, size_t len, const uint64_t* nonces, size_t n,
+                                int threads, uint64_t* hashes) {
+    using namespace hm;
+    if ((!msg && len) || (n && (!nonces || !hashes))) return HM_ERR_INVALID;
+    try {
+        if (n == 0) return HM_OK;
+        static const uint8_t empty = 0;
+        const MsgPlan mp = plan_message(msg ? msg : &empty, msg ? len : 0);
+        const CompressFn compress = pick_compress();
+        // every element is written by exactly one thread; a failed start of a
+        // thread leaves a prefix written, so the answer goes through a copy
+        std::vector<uint64_t> out(n);
+        const int rc = over_list(
+            n, threads, [](unsigned) {},
+            [&](unsigned, size_t a, size_t b) { hash_part(mp, nonces, a, b, compress, out.data()); });
+        if (rc) return rc;
+        memcpy(hashes, out.data(), n * sizeof(uint64_t));
+        return HM_OK;
+    } catch (const std::bad_alloc&) {
+        return HM_ERR_NOMEM;
+    } catch (...) {
+        return HM_ERR_INTERNAL;
+    }
+}
+
+extern "C" int hm_verify_cpu(const uint8_t* msg, size_t len, const hm_result* recs, size_t n,
+                             uint64_t target, int threads, uint64_t* bad_idx, size_t cap,
+                             uint64_t* bad) {
+    using namespace hm;
+    if (!bad || (!msg && len) || (n && !recs) || cap > HM_VERIFY_CAP_MAX || (cap && !bad_idx))
+        return HM_ERR_INVALID;
+    try {
+        if (n == 0) {
+            *bad = 0;
+            return HM_OK;
+        }
+        static const uint8_t empty = 0;
+        const MsgPlan mp = plan_message(msg ? msg : &empty, msg ? len : 0);
+        const CompressFn compress = pick_compress();
+        std::vector<VerifyPart> part;
+        const int rc = over_list(
+            n, threads, [&](unsigned parts) { part.resize(parts); },
+            [&](unsigned t, size_t a, size_t b) {
+                verify_part(mp, recs, a, b, target, cap, compress, &part[t]);
+            });
+        if (rc) return rc;
+        uint64_t sum = 0;
+        for (const VerifyPart& p : part) {
+            if (p.failed) return HM_ERR_NOMEM;
+            sum += p.count;  // <= n
+        }
+        if (sum <= cap) {
+            // the parts ascend and each is ascending: so is the concatenation
+            size_t at = 0;
+            for (const VerifyPart& p : part) {
+                if (!p.idx.empty()) memcpy(bad_idx + at, p.idx.data(), p.idx.size() * sizeof(uint64_t));
+                at += p.idx.size();
+            }
+        }
+        *bad = sum;
         return HM_OK;
     } catch (const std::bad_alloc&) {
         return HM_ERR_NOMEM;

@@ -266,6 +266,31 @@ struct CollectGenericArgs {
     CollectArgs k;
 };
 
+// ---------------------------------------------------------------------------
+// hm_hash_many / hm_verify (verify_kernels.hip, DESIGN.md "Recheck a list"):
+// Hash(msg, nonce) for a LIST of arbitrary nonces, one element per lane, each
+// lane with its own digit count and tail layout.  hm_hash_list_kernel<false>
+// stores the hashes; <true> compares 16-byte (hash, nonce) records against
+// the hash and a target and reports the indices of the bad ones through
+// CollectArgs' protocol applied to indices (two zeroed 64-bit words per
+// device and a buffer of `cap` indices).
+// ---------------------------------------------------------------------------
+struct VerifyArgs {
+    const uint64_t* in;   // VERIFY: n records of 2 x u64 (hash, nonce); else n nonces
+    uint64_t* hashes;     // !VERIFY: n hashes out (may be `in`: a lane touches its own slot only)
+    uint64_t* total;      // VERIFY: += the wave's bad records, once per wave
+    uint64_t* cursor;     // VERIFY: slot reservations (cap > 0 only)
+    uint64_t* idx;        // VERIFY: cap global indices; null when cap == 0
+    uint64_t target;      // VERIFY: a record with hash >= target is bad
+    uint64_t index0;      // VERIFY: the global index of in[0]
+    uint64_t bits0;       // (len + 1) * 8: the message bit length is bits0 + 8 d
+    uint32_t n;           // list elements of this launch (<= 2^22)
+    uint32_t cap;         // <= HM_VERIFY_CAP_MAX
+    uint32_t r;           // prefix-remainder bytes in front of the digits
+    uint32_t pw[16];      // prefix remainder, big-endian words, zero padded
+    uint32_t mid[8];      // midstate after the constant blocks
+};
+
 // Launchers of the auxiliary kernels (kernels.hip; return hipError_t of the
 // launch).  The scan kernels (scan_kernels.hip: hm_tiled_kernel<W1,
 // STRADDLE, TRAILER>, hm_chained_kernel, hm_generic_kernel and their

@@ -19,7 +19,10 @@
  * reference does not have: the LOWEST nonce whose hash is below a target,
  * found without scanning the rest of the range.  hm_collect (ABI 1.11) adds
  * its share-collection form: EVERY nonce whose hash is below a target, and
- * their exact count.
+ * their exact count.  The list calls of ABI 1.12 are the receiving side of
+ * that exchange, which the reference's server lacks (server.go:273 believes
+ * the hash it is sent): the hash at every nonce of a list, and which
+ * (hash, nonce) records of a list are wrong or not below a target.
  *
  * The cgo binding a maintainer adds to the Go miner is in INTEGRATION.md.
  *
@@ -409,6 +412,84 @@ typedef struct hm_collect_stats {
  * it; >= HM_COLLECT_STATS_SIZE_1_11) of the last successful collect's stats;
  * HM_ERR_INVALID before the first one. */
 int hm_collect_stats_sized(const hm_ctx *ctx, hm_collect_stats *out, size_t size);
+
+/* ABI 1.12: recheck a list.  The receiving side of share collection: a pool
+ * hands out work at a share target and miners return lists of (hash, nonce)
+ * records; the reference server believes them (server.go:273 only compares
+ * the hash).  Two calls over one kernel that hashes a LIST of arbitrary
+ * nonces, one per GPU lane, each with its own digit count:
+ *
+ *   hm_hash_many:  hashes[i] = Hash(msg, nonces[i]) for i < n.
+ *   hm_verify:     record i is BAD iff
+ *                      recs[i].hash != Hash(msg, recs[i].nonce)
+ *                   or recs[i].hash >= target            (strict '<', as in find and collect)
+ *
+ * target = 0 makes every record bad.  target = UINT64_MAX checks the hash
+ * alone, except that a record whose hash is UINT64_MAX is bad even when that
+ * is its true hash.  Nonces may repeat, come in any order and have any digit
+ * count 1..20; nonces 0 and UINT64_MAX are ordinary.  No range or duplicate
+ * check is done: a caller does those on the host in one pass over the list.
+ *
+ * *bad = the number of bad records, always exact.  The size-query idiom of
+ * the collect call applies:
+ *   *bad <= cap: bad_idx[0 .. *bad) holds the indices of the bad records,
+ *                ASCENDING; nothing at or beyond bad_idx[*bad] is touched.
+ *   *bad >  cap: bad_idx is not written at all.
+ *   cap == 0 with bad_idx == NULL is the pure count.
+ * Only the count and the indices cross the bus back.  The hash-list call
+ * writes all n hashes, or nothing if it does not return HM_OK.
+ *
+ * n == 0 returns HM_OK with *bad = 0 and enqueues nothing.  msg == NULL with
+ * len == 0 is the empty message.  HM_ERR_INVALID: n > 0 with a NULL list,
+ * hashes == NULL with n > 0, cap > HM_VERIFY_CAP_MAX, cap > 0 with
+ * bad_idx == NULL, bad == NULL.  Outputs are written only on HM_OK.  An
+ * abandoned context returns HM_ERR_TIMEOUT.  HM_OPT_DEADLINE_MS applies (auto:
+ * 2 s plus 8 x a per-record time, there being no range to model); no other
+ * option does.  Both calls use stream 0 only and create no stream: the list is
+ * cut contiguously across the context's devices in even shares, each share
+ * into chunks of at most 2^22 elements (copy in, one launch, for hashes a copy
+ * out), all devices' work is enqueued before the host waits on any, and the
+ * host sums the counts and sorts the indices.  The caller's memory is not
+ * registered or altered.  Each device keeps a chunk buffer (at most 64 MiB)
+ * and a buffer of `cap` indices, made on first use, grown when needed and
+ * kept until the context is closed.  Neither call changes what
+ * hm_scan_stats*, hm_find_stats_sized or hm_collect_stats_sized report. */
+#define HM_VERIFY_CAP_MAX (1u << 20) /* bad indices returned at most */
+int hm_hash_many(hm_ctx *ctx, const uint8_t *msg, size_t len, const uint64_t *nonces, size_t n,
+                 uint64_t *hashes);
+int hm_verify(hm_ctx *ctx, const uint8_t *msg, size_t len, const hm_result *recs, size_t n,
+              uint64_t target, uint64_t *bad_idx, size_t cap, uint64_t *bad);
+
+/* The same answers on the host's cores, no GPU, under the same contract
+ * (`threads` as hm_scan_cpu's; the compression too: x86 SHA extensions,
+ * HM_CPU_NO_SHA=1 for portable C).  Each thread takes a contiguous part of
+ * the list; the parts' bad indices are concatenated in order. */
+int hm_hash_many_cpu(const uint8_t *msg, size_t len, const uint64_t *nonces, size_t n,
+                     int threads, uint64_t *hashes);
+int hm_verify_cpu(const uint8_t *msg, size_t len, const hm_result *recs, size_t n,
+                  uint64_t target, int threads, uint64_t *bad_idx, size_t cap, uint64_t *bad);
+
+/* Accounting of the most recent successful hm_hash_many or hm_verify on a
+ * context (the hash-list call reports bad = 0).  The struct only grows at
+ * its end. */
+typedef struct hm_verify_stats {
+    double wall_ms;    /* host wall time of the call                             */
+    double kernel_ms;  /* summed HIP-event time of its launches                  */
+    double copy_ms;    /* summed HIP-event time of its copies to and from the
+                          device (the chunks in; for hashes, the chunks out)    */
+    uint64_t records;  /* list elements: n                                       */
+    uint64_t bad;      /* the call's *bad                                        */
+    int32_t launches;  /* kernel launches issued (one per chunk)                 */
+    int32_t ndev;      /* devices of the context                                 */
+    int32_t overflow;  /* 1: *bad > cap, bad_idx was not written; else 0         */
+    int32_t reserved;
+} hm_verify_stats;
+#define HM_VERIFY_STATS_SIZE_1_12 56 /* ABI 1.12 */
+
+/* Writes at most `size` bytes (pass sizeof the struct as the caller compiled
+ * it; >= HM_VERIFY_STATS_SIZE_1_12) of the last successful call's stats;
+ * HM_ERR_INVALID before the first one. */
+int hm_verify_stats_sized(const hm_ctx *ctx, hm_verify_stats *out, size_t size);
 
 int hm_set_option(hm_ctx *ctx, int opt, int64_t value);
 

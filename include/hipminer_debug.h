@@ -50,6 +50,11 @@ extern "C" {
                                   tasks a workgroup fetches per work-queue
                                   atomic in the per-segment kernels; 0 (default)
                                   = 4, and 16 for launches of >= 10^11 nonces */
+#define HM_OPT_VERIFY_CHUNK 19  /* test hook (a multiple of 64 in [64, 2^22];
+                                  0 = default 2^22; ABI 1.12): list elements
+                                  per chunk and device of the list calls, so a
+                                  list of a few hundred records crosses chunk
+                                  boundaries (ids 16 and 18 stay retired)      */
 
 /* The embedded scan code object: *p = its first byte, returns its size.
  * bench.py hashes these bytes to match a PMC summary to the build that runs. */
