@@ -48,7 +48,8 @@
 // records by nonce, so the answer does not.
 //
 // Compiled like scan_kernels.hip (device-only -S, align_loops.py, linked into
-// hipminer_scan.hsaco) and looked up by mangled name (api.cpp).
+// hipminer_scan.hsaco) and looked up by mangled name (kernel_name() in
+// seg_walk.cpp).
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
@@ -57,15 +58,6 @@
 #include "sha_device.hpp"
 
 namespace hm {
-
-#ifndef HM_TILED_WAVES_PER_EU
-#define HM_TILED_WAVES_PER_EU 0
-#endif
-#if HM_TILED_WAVES_PER_EU > 0
-#define HM_COLLECT_TILED_BOUNDS __launch_bounds__(kBlock, HM_TILED_WAVES_PER_EU)
-#else
-#define HM_COLLECT_TILED_BOUNDS __launch_bounds__(kBlock)
-#endif
 
 DEV WaveCollect collect_begin(const CollectArgs& C) {
     WaveCollect c;
@@ -76,14 +68,9 @@ DEV WaveCollect collect_begin(const CollectArgs& C) {
     c.cap = C.cap;
     return c;
 }
-// The wave's count into the device total, once, at the wave's exit.
-DEV void collect_end(const CollectArgs& C, const WaveCollect& c) {
-    if (c.count && __lane_id() == 0)
-        __hip_atomic_fetch_add(C.total, c.count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 template <int W1, bool STRADDLE, bool TRAILER>
-__global__ void HM_COLLECT_TILED_BOUNDS hm_collect_tiled_kernel(const CollectTiledArgs CA) {
+__global__ void HM_TILED_BOUNDS hm_collect_tiled_kernel(const CollectTiledArgs CA) {
     const TiledArgs& A = CA.t;
     WaveCollect col = collect_begin(CA.k);
     WaveSums sums;  // unused (CSUM = false)
@@ -93,22 +80,13 @@ __global__ void HM_COLLECT_TILED_BOUNDS hm_collect_tiled_kernel(const CollectTil
     for (;;) {
         const uint32_t task = lds_dequeue(&queue, A.counter, A.lds_shift);
         if (task >= A.ntasks) break;
-        uint32_t unit = task, t1_begin = 0, t1_end = 10;
-        if (task >= A.nbig) {
-            const uint32_t k = task - A.nbig;
-            const uint32_t u = k / kSplit;
-            unit = A.nbig + u;
-            t1_begin = k - u * kSplit;
-            t1_end = t1_begin + 1;
-        }
-        const uint32_t tile = unit / A.tpt;
-        const uint32_t chunk = unit - tile * A.tpt;
-        const uint64_t tile_base = (A.tile0 + tile) * A.pow10V;
+        const TiledTask T = tiled_decode(A, task);
         tiled_task<W1, STRADDLE, TRAILER, false>(
-            A.rec + (size_t)tile * kRecWords, chunk, t1_begin, t1_end, tile_base, A.seg_lo,
-            A.seg_hi, A.vmax, A.q, A.lane_shift, A.loop_shift, A.s0_loop, A.trailer_kw, col, sums);
+            A.rec + (size_t)T.tile * kRecWords, T.chunk, T.t1_begin, T.t1_end,
+            (A.tile0 + T.tile) * A.pow10V, A.seg_lo, A.seg_hi, A.vmax, A.q, A.lane_shift,
+            A.loop_shift, A.s0_loop, A.trailer_kw, col, sums);
     }
-    collect_end(CA.k, col);
+    wave_total(CA.k.total, col.count);
 }
 
 __global__ void __launch_bounds__(kBlock) hm_collect_chained_kernel(const CollectChainedArgs CA) {
@@ -122,28 +100,12 @@ __global__ void __launch_bounds__(kBlock) hm_collect_chained_kernel(const Collec
     for (;;) {
         const uint32_t task = lds_dequeue(&queue, A.counter, A.lds_shift);
         if (task >= A.ntasks) break;
-        uint32_t unit = task, part = 0, nparts = 1;
-        if (task >= A.nbig) {
-            const uint32_t k = task - A.nbig;
-            const uint32_t u = k / kSplit;
-            unit = A.nbig + u;
-            part = k - u * kSplit;
-            nparts = kSplit;
-        }
-        const uint32_t tile = unit / per_tile;
-        const uint32_t rem = unit - tile * per_tile;
-        const uint32_t chunk = rem / A.ntc;
-        const uint32_t tc = rem - chunk * A.ntc;
-        const uint32_t piece = (A.tch + nparts - 1) / nparts;
-        const uint32_t t_begin = tc * A.tch + part * piece;
-        uint32_t t_end = tc * A.tch + A.tch;
-        if (t_end > A.nloop) t_end = A.nloop;
-        if (t_end > t_begin + piece) t_end = t_begin + piece;
-        const uint64_t tile_base = (A.tile0 + tile) * A.pow10qf + A.ebase;
-        chained_task<false>(A.rec + (size_t)tile * kRecWords, chunk, t_begin, t_end, tile_base,
-                            A.pow10f, A.seg_lo, A.seg_hi, A.vmax, A.q, A.kwt, col, sums);
+        const ChainedTask T = chained_decode(A, per_tile, task);
+        chained_task<false>(A.rec + (size_t)T.tile * kRecWords, T.chunk, T.t_begin, T.t_end,
+                            (A.tile0 + T.tile) * A.pow10qf + A.ebase, A.pow10f, A.seg_lo, A.seg_hi,
+                            A.vmax, A.q, A.kwt, col, sums);
     }
-    collect_end(CA.k, col);
+    wave_total(CA.k.total, col.count);
 }
 
 // One nonce per lane, any layout.  Wave w of the grid takes the 64 nonces
@@ -158,6 +120,9 @@ __global__ void __launch_bounds__(kBlock) hm_collect_generic_kernel(const Collec
         // lanes past the segment's end repeat the step's first nonce: surplus
         const bool live = A.count_m1 - kb >= lane;
         const uint64_t n = A.seg_lo + kb + (live ? lane : 0u);
+        // hash_nonce's text (sha_device.hpp), kept here as this kernel's own
+        // copy: through the helper the kernel measured 1-2 % slower
+        // (profiles/README.md, dedup/)
         uint32_t w[32];
         build_tail(w, A.pw, A.r, A.d, 0, n, A.nb, A.total_bits);
         uint32_t st[8];
@@ -178,30 +143,13 @@ __global__ void __launch_bounds__(kBlock) hm_collect_generic_kernel(const Collec
         if (A.count_m1 - kb < stride) break;
         kb += stride;
     }
-    collect_end(CA.k, col);
+    wave_total(CA.k.total, col.count);
 }
 
-// Every tiled layout the planner can pick (as scan_kernels.hip).
+// Every tiled layout the planner can pick.
 #define HM_COLLECT_INST(W, S, T) \
     template __global__ void hm_collect_tiled_kernel<W, S, T>(const CollectTiledArgs);
-#define HM_COLLECT_INST_S(W, T) HM_COLLECT_INST(W, false, T) HM_COLLECT_INST(W, true, T)
-HM_COLLECT_INST_S(1, false)
-HM_COLLECT_INST_S(2, false)
-HM_COLLECT_INST_S(3, false)
-HM_COLLECT_INST_S(4, false)
-HM_COLLECT_INST_S(5, false)
-HM_COLLECT_INST_S(6, false)
-HM_COLLECT_INST_S(7, false)
-HM_COLLECT_INST_S(8, false)
-HM_COLLECT_INST_S(9, false)
-HM_COLLECT_INST_S(10, false)
-HM_COLLECT_INST_S(11, false)
-HM_COLLECT_INST_S(12, false)
-HM_COLLECT_INST_S(13, false)
-HM_COLLECT_INST_S(13, true)
-HM_COLLECT_INST_S(14, true)
-HM_COLLECT_INST_S(15, true)
-#undef HM_COLLECT_INST_S
+HM_FOR_EACH_TILED_LAYOUT(HM_COLLECT_INST)
 #undef HM_COLLECT_INST
 
 }  // namespace hm

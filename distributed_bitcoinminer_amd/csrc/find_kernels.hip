@@ -39,7 +39,8 @@
 // The host recomputes the answer's hash (host_hash): only the nonce crosses.
 //
 // Compiled like scan_kernels.hip (device-only -S, align_loops.py, linked into
-// hipminer_scan.hsaco) and looked up by mangled name (api.cpp).
+// hipminer_scan.hsaco) and looked up by mangled name (kernel_name() in
+// seg_walk.cpp).
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
@@ -48,15 +49,6 @@
 #include "sha_device.hpp"
 
 namespace hm {
-
-#ifndef HM_TILED_WAVES_PER_EU
-#define HM_TILED_WAVES_PER_EU 0
-#endif
-#if HM_TILED_WAVES_PER_EU > 0
-#define HM_FIND_TILED_BOUNDS __launch_bounds__(kBlock, HM_TILED_WAVES_PER_EU)
-#else
-#define HM_FIND_TILED_BOUNDS __launch_bounds__(kBlock)
-#endif
 
 // The stop word, wave-uniform: one lane loads, the wave shares the value.
 DEV uint64_t find_stop(const FindArgs& F) {
@@ -93,7 +85,7 @@ DEV bool find_enter(const FindArgs& F, WaveFirst& first, uint64_t task_lo, uint6
 }
 
 template <int W1, bool STRADDLE, bool TRAILER>
-__global__ void HM_FIND_TILED_BOUNDS hm_find_tiled_kernel(const FindTiledArgs FA) {
+__global__ void HM_TILED_BOUNDS hm_find_tiled_kernel(const FindTiledArgs FA) {
     const TiledArgs& A = FA.t;
     const FindArgs& F = FA.f;
     WaveFirst first = find_first(F);
@@ -106,23 +98,15 @@ __global__ void HM_FIND_TILED_BOUNDS hm_find_tiled_kernel(const FindTiledArgs FA
     for (;;) {
         const uint32_t task = lds_dequeue(&queue, A.counter, A.lds_shift);
         if (task >= A.ntasks) break;
-        uint32_t unit = task, t1_begin = 0, t1_end = 10;
-        if (task >= A.nbig) {
-            const uint32_t k = task - A.nbig;
-            const uint32_t u = k / kSplit;
-            unit = A.nbig + u;
-            t1_begin = k - u * kSplit;
-            t1_end = t1_begin + 1;
-        }
-        const uint32_t tile = unit / A.tpt;
-        const uint32_t chunk = unit - tile * A.tpt;
-        const uint64_t tile_base = (A.tile0 + tile) * A.pow10V;
+        const TiledTask T = tiled_decode(A, task);
+        const uint64_t tile_base = (A.tile0 + T.tile) * A.pow10V;
         // lane 0's first loop step: the task's smallest nonce
-        const uint64_t task_lo = tile_base + (uint64_t)chunk * (kWaveSize * 100u) + t1_begin * 10u;
+        const uint64_t task_lo =
+            tile_base + (uint64_t)T.chunk * (kWaveSize * 100u) + T.t1_begin * 10u;
         uint64_t before;
         if (!find_enter(F, first, task_lo, &before)) break;
         tiled_task<W1, STRADDLE, TRAILER, false>(
-            A.rec + (size_t)tile * kRecWords, chunk, t1_begin, t1_end, tile_base, A.seg_lo,
+            A.rec + (size_t)T.tile * kRecWords, T.chunk, T.t1_begin, T.t1_end, tile_base, A.seg_lo,
             A.seg_hi, A.vmax, A.q, A.lane_shift, A.loop_shift, A.s0_loop, A.trailer_kw, first, sums);
         ++ran;
         if (first.nonce < before) find_publish(F, first.nonce);
@@ -144,31 +128,16 @@ __global__ void __launch_bounds__(kBlock) hm_find_chained_kernel(const FindChain
     for (;;) {
         const uint32_t task = lds_dequeue(&queue, A.counter, A.lds_shift);
         if (task >= A.ntasks) break;
-        uint32_t unit = task, part = 0, nparts = 1;
-        if (task >= A.nbig) {
-            const uint32_t k = task - A.nbig;
-            const uint32_t u = k / kSplit;
-            unit = A.nbig + u;
-            part = k - u * kSplit;
-            nparts = kSplit;
-        }
-        const uint32_t tile = unit / per_tile;
-        const uint32_t rem = unit - tile * per_tile;
-        const uint32_t chunk = rem / A.ntc;
-        const uint32_t tc = rem - chunk * A.ntc;
-        const uint32_t piece = (A.tch + nparts - 1) / nparts;
-        const uint32_t t_begin = tc * A.tch + part * piece;
-        uint32_t t_end = tc * A.tch + A.tch;
-        if (t_end > A.nloop) t_end = A.nloop;
-        if (t_end > t_begin + piece) t_end = t_begin + piece;
-        const uint64_t tile_base = (A.tile0 + tile) * A.pow10qf + A.ebase;
+        const ChainedTask T = chained_decode(A, per_tile, task);
+        const uint64_t tile_base = (A.tile0 + T.tile) * A.pow10qf + A.ebase;
         // lane 0's first loop value: the task's smallest nonce (its lanes
         // stride pow10f, so the task reaches 63 * pow10f beyond it)
-        const uint64_t task_lo = tile_base + (uint64_t)chunk * kWaveSize * A.pow10f + t_begin;
+        const uint64_t task_lo = tile_base + (uint64_t)T.chunk * kWaveSize * A.pow10f + T.t_begin;
         uint64_t before;
         if (!find_enter(F, first, task_lo, &before)) break;
-        chained_task<false>(A.rec + (size_t)tile * kRecWords, chunk, t_begin, t_end, tile_base,
-                            A.pow10f, A.seg_lo, A.seg_hi, A.vmax, A.q, A.kwt, first, sums);
+        chained_task<false>(A.rec + (size_t)T.tile * kRecWords, T.chunk, T.t_begin, T.t_end,
+                            tile_base, A.pow10f, A.seg_lo, A.seg_hi, A.vmax, A.q, A.kwt, first,
+                            sums);
         ++ran;
         if (first.nonce < before) find_publish(F, first.nonce);
     }
@@ -194,6 +163,9 @@ __global__ void __launch_bounds__(kBlock) hm_find_generic_kernel(const FindGener
         // lanes past the segment's end repeat the step's first nonce
         const bool live = A.count_m1 - kb >= lane;
         const uint64_t n = A.seg_lo + kb + (live ? lane : 0u);
+        // hash_nonce's text (sha_device.hpp), kept here as this kernel's own
+        // copy: through the helper hipcc loads the whole argument block before
+        // the early exit above and the kernel spills 10 more SGPRs (83 for 73)
         uint32_t w[32];
         build_tail(w, A.pw, A.r, A.d, 0, n, A.nb, A.total_bits);
         uint32_t st[8];
@@ -223,27 +195,10 @@ __global__ void __launch_bounds__(kBlock) hm_find_generic_kernel(const FindGener
     find_count(F, ran);
 }
 
-// Every tiled layout the planner can pick (as scan_kernels.hip).
+// Every tiled layout the planner can pick.
 #define HM_FIND_INST(W, S, T) \
     template __global__ void hm_find_tiled_kernel<W, S, T>(const FindTiledArgs);
-#define HM_FIND_INST_S(W, T) HM_FIND_INST(W, false, T) HM_FIND_INST(W, true, T)
-HM_FIND_INST_S(1, false)
-HM_FIND_INST_S(2, false)
-HM_FIND_INST_S(3, false)
-HM_FIND_INST_S(4, false)
-HM_FIND_INST_S(5, false)
-HM_FIND_INST_S(6, false)
-HM_FIND_INST_S(7, false)
-HM_FIND_INST_S(8, false)
-HM_FIND_INST_S(9, false)
-HM_FIND_INST_S(10, false)
-HM_FIND_INST_S(11, false)
-HM_FIND_INST_S(12, false)
-HM_FIND_INST_S(13, false)
-HM_FIND_INST_S(13, true)
-HM_FIND_INST_S(14, true)
-HM_FIND_INST_S(15, true)
-#undef HM_FIND_INST_S
+HM_FOR_EACH_TILED_LAYOUT(HM_FIND_INST)
 #undef HM_FIND_INST
 
 }  // namespace hm

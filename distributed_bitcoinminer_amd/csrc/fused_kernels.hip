@@ -113,33 +113,20 @@ DEV void fused_generic(FusedArgsK* A, const FusedSeg& S, uint32_t k, uint32_t pp
         if (nb0 > S.seg_hi || nb0 < S.seg_lo) break;  // past the end (or wrapped)
         const uint64_t n = nb0 + lane;
         const bool in = n >= nb0 && n <= S.seg_hi;  // no wrap past 2^64-1
-        uint32_t w[32];
-        build_tail(w, pw, A->r, S.d, 0, in ? n : nb0, S.nb, S.total_bits);
-        uint32_t st[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) st[i] = mid[i];
-        uint32_t m[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) m[i] = w[i];
-        d_compress(st, m);
-        if (S.nb == 2) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) m[i] = w[16 + i];
-            d_compress(st, m);
-        }
+        uint32_t h0, h1;
+        hash_nonce(pw, A->r, S.d, S.nb, S.total_bits, mid, in ? n : nb0, h0, h1);
         if constexpr (CSUM) {
             if (in) {
-                sums.sum += ((uint64_t)st[0] << 32) | st[1];
+                sums.sum += ((uint64_t)h0 << 32) | h1;
                 ++sums.cnt;
             }
         }
-        take_step(best, in && st[0] <= best.hi, st[0], st[1], nb0, lane, S.seg_lo, S.seg_hi);
+        take_step(best, in && h0 <= best.hi, h0, h1, nb0, lane, S.seg_lo, S.seg_hi);
     }
 }
 
 #define HM_FUSED_CASE(W, S, T) \
     case (W) * 4 + (S) * 2 + (T): fused_tiled<W, S, T, CSUM>(A, S_, k, pp, np, best, sums); break;
-#define HM_FUSED_CASE_S(W, T) HM_FUSED_CASE(W, false, T) HM_FUSED_CASE(W, true, T)
 
 template <bool CSUM>
 DEV void fused_body(FusedArgsK* A) {
@@ -197,22 +184,7 @@ DEV void fused_body(FusedArgsK* A) {
         const FusedSeg S_ = A->segs[i];  // scalar loads of one descriptor
         const uint32_t k = task - (i ? A->segs[i - 1].task_end : 0u);
         switch (S_.variant) {
-            HM_FUSED_CASE_S(1, false)
-            HM_FUSED_CASE_S(2, false)
-            HM_FUSED_CASE_S(3, false)
-            HM_FUSED_CASE_S(4, false)
-            HM_FUSED_CASE_S(5, false)
-            HM_FUSED_CASE_S(6, false)
-            HM_FUSED_CASE_S(7, false)
-            HM_FUSED_CASE_S(8, false)
-            HM_FUSED_CASE_S(9, false)
-            HM_FUSED_CASE_S(10, false)
-            HM_FUSED_CASE_S(11, false)
-            HM_FUSED_CASE_S(12, false)
-            HM_FUSED_CASE_S(13, false)
-            HM_FUSED_CASE_S(13, true)
-            HM_FUSED_CASE_S(14, true)
-            HM_FUSED_CASE_S(15, true)
+            HM_FOR_EACH_TILED_LAYOUT(HM_FUSED_CASE)
             case kVarChained: fused_chained<CSUM>(A, S_, k, pp, np, best, sums); break;
             default: fused_generic<CSUM>(A, S_, k, pp, np, best, sums); break;
         }
@@ -227,7 +199,6 @@ DEV void fused_body(FusedArgsK* A) {
     }
 }
 
-#undef HM_FUSED_CASE_S
 #undef HM_FUSED_CASE
 
 // The argument block is the kernel's only (explicit) parameter, so it starts

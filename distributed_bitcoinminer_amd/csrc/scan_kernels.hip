@@ -21,9 +21,10 @@
 //
 // This file is compiled for the device only (`--cuda-device-only -S`); the
 // Makefile passes the assembly through align_loops.py (instruction placement
-// of the hot loops) and links it into the code object that
-// api.cpp embeds and loads with hipModuleLoadData.  Kernels are therefore
-// looked up by their mangled names (scan_symbol() in api.cpp).
+// of the hot loops) and links it into the code object that the
+// library embeds (scan_blob.S) and device.cpp loads with hipModuleLoadData.
+// Kernels are therefore looked up by their mangled names (kernel_name() in
+// seg_walk.cpp).
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
@@ -36,14 +37,6 @@ namespace hm {
 // ---------------------------------------------------------------------------
 // Tiled scan (the hot kernel)
 // ---------------------------------------------------------------------------
-#ifndef HM_TILED_WAVES_PER_EU
-#define HM_TILED_WAVES_PER_EU 0
-#endif
-#if HM_TILED_WAVES_PER_EU > 0
-#define HM_TILED_BOUNDS __launch_bounds__(kBlock, HM_TILED_WAVES_PER_EU)
-#else
-#define HM_TILED_BOUNDS __launch_bounds__(kBlock)
-#endif
 
 // CSUM: checked variant (coverage sum and count of the hashed keys).
 template <int W1, bool STRADDLE, bool TRAILER, bool CSUM>
@@ -58,20 +51,11 @@ DEV void tiled_body(const TiledArgs& A) {
         const uint32_t task = lds_dequeue(&queue, A.counter, A.lds_shift);
         if (task >= A.ntasks) break;
         // guided sizes: whole units first, then tenths (one tens digit each)
-        uint32_t unit = task, t1_begin = 0, t1_end = 10;
-        if (task >= A.nbig) {
-            const uint32_t k = task - A.nbig;
-            const uint32_t u = k / kSplit;
-            unit = A.nbig + u;
-            t1_begin = k - u * kSplit;
-            t1_end = t1_begin + 1;
-        }
-        const uint32_t tile = unit / A.tpt;
-        const uint32_t chunk = unit - tile * A.tpt;
+        const TiledTask T = tiled_decode(A, task);
         tiled_task<W1, STRADDLE, TRAILER, CSUM>(
-            A.rec + (size_t)tile * kRecWords, chunk, t1_begin, t1_end, (A.tile0 + tile) * A.pow10V,
-            A.seg_lo, A.seg_hi, A.vmax, A.q, A.lane_shift, A.loop_shift, A.s0_loop, A.trailer_kw,
-            best, sums);
+            A.rec + (size_t)T.tile * kRecWords, T.chunk, T.t1_begin, T.t1_end,
+            (A.tile0 + T.tile) * A.pow10V, A.seg_lo, A.seg_hi, A.vmax, A.q, A.lane_shift,
+            A.loop_shift, A.s0_loop, A.trailer_kw, best, sums);
     }
     wave_store<CSUM>(A.cand, A.sums, wslot, best, sums);
 }
@@ -105,25 +89,9 @@ DEV void chained_body(const ChainedArgs& A) {
         const uint32_t task = lds_dequeue(&queue, A.counter, A.lds_shift);
         if (task >= A.ntasks) break;
         // guided sizes: whole loop chunks first, then kSplit pieces of each
-        uint32_t unit = task, part = 0, nparts = 1;
-        if (task >= A.nbig) {
-            const uint32_t k = task - A.nbig;
-            const uint32_t u = k / kSplit;
-            unit = A.nbig + u;
-            part = k - u * kSplit;
-            nparts = kSplit;
-        }
-        const uint32_t tile = unit / per_tile;
-        const uint32_t rem = unit - tile * per_tile;
-        const uint32_t chunk = rem / A.ntc;
-        const uint32_t tc = rem - chunk * A.ntc;
-        const uint32_t piece = (A.tch + nparts - 1) / nparts;
-        const uint32_t t_begin = tc * A.tch + part * piece;
-        uint32_t t_end = tc * A.tch + A.tch;
-        if (t_end > A.nloop) t_end = A.nloop;
-        if (t_end > t_begin + piece) t_end = t_begin + piece;
-        chained_task<CSUM>(A.rec + (size_t)tile * kRecWords, chunk, t_begin, t_end,
-                           (A.tile0 + tile) * A.pow10qf + A.ebase, A.pow10f, A.seg_lo, A.seg_hi,
+        const ChainedTask T = chained_decode(A, per_tile, task);
+        chained_task<CSUM>(A.rec + (size_t)T.tile * kRecWords, T.chunk, T.t_begin, T.t_end,
+                           (A.tile0 + T.tile) * A.pow10qf + A.ebase, A.pow10f, A.seg_lo, A.seg_hi,
                            A.vmax, A.q, A.kwt, best, sums);
     }
     wave_store<CSUM>(A.cand, A.sums, wslot, best, sums);
@@ -147,21 +115,9 @@ DEV void generic_body(const GenericArgs& A) {
     uint64_t csum = 0, ccnt = 0;  // CSUM only
     for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k <= A.count_m1;) {
         const uint64_t n = A.seg_lo + k;
-        uint32_t w[32];
-        build_tail(w, A.pw, A.r, A.d, 0, n, A.nb, A.total_bits);
-        uint32_t st[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) st[j] = A.mid[j];
-        uint32_t m[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) m[j] = w[j];
-        d_compress(st, m);
-        if (A.nb == 2) {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) m[j] = w[16 + j];
-            d_compress(st, m);
-        }
-        const uint64_t key = ((uint64_t)st[0] << 32) | st[1];
+        uint32_t h0, h1;
+        hash_nonce(A.pw, A.r, A.d, A.nb, A.total_bits, A.mid, n, h0, h1);
+        const uint64_t key = ((uint64_t)h0 << 32) | h1;
         if constexpr (CSUM) { csum += key; ++ccnt; }
         if (key < bk || (key == bk && n < bn)) { bk = key; bn = n; }
         if (A.count_m1 - k < stride) break;
@@ -184,29 +140,11 @@ __global__ void __launch_bounds__(kBlock) hm_generic_csum_kernel(const GenericAr
     generic_body<true>(A);
 }
 
-// Every tiled layout the planner can pick (plan.cpp layout): one tail block
-// with W1 = 1..13, or W1 = 13..15 followed by a constant trailer block.
+// Every tiled layout the planner can pick, plain and checked.
 #define HM_TILED_INST(W, S, T)                                                 \
     template __global__ void hm_tiled_kernel<W, S, T>(const TiledArgs);        \
     template __global__ void hm_tiled_csum_kernel<W, S, T>(const TiledArgs);
-#define HM_TILED_INST_S(W, T) HM_TILED_INST(W, false, T) HM_TILED_INST(W, true, T)
-HM_TILED_INST_S(1, false)
-HM_TILED_INST_S(2, false)
-HM_TILED_INST_S(3, false)
-HM_TILED_INST_S(4, false)
-HM_TILED_INST_S(5, false)
-HM_TILED_INST_S(6, false)
-HM_TILED_INST_S(7, false)
-HM_TILED_INST_S(8, false)
-HM_TILED_INST_S(9, false)
-HM_TILED_INST_S(10, false)
-HM_TILED_INST_S(11, false)
-HM_TILED_INST_S(12, false)
-HM_TILED_INST_S(13, false)
-HM_TILED_INST_S(13, true)
-HM_TILED_INST_S(14, true)
-HM_TILED_INST_S(15, true)
-#undef HM_TILED_INST_S
+HM_FOR_EACH_TILED_LAYOUT(HM_TILED_INST)
 #undef HM_TILED_INST
 
 }  // namespace hm

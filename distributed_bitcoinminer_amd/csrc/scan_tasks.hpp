@@ -1,6 +1,9 @@
 // scan_tasks.hpp -- one task of each scan kernel kind, shared by the
-// per-segment kernels (scan_kernels.hip) and the fused small-request kernel
-// (fused_kernels.hip).
+// per-segment kernels (scan_kernels.hip, find_kernels.hip,
+// collect_kernels.hip) and the fused small-request kernel
+// (fused_kernels.hip): the reductions a task folds its nonces into, the task
+// dispenser, the decoding of a task id, the list of tiled layouts and the
+// task bodies.
 //
 // Replaces the miner's sequential loop (cmu440/bitcoin/miner/miner.go:46-59)
 // over bitcoin.Hash (cmu440/bitcoin/hash.go:13-17) for one wave's share of
@@ -144,6 +147,99 @@ DEV void take_step(WaveCollect& c, bool cand, uint32_t h0, uint32_t h1, uint64_t
         }
     }
 }
+
+// The wave's count into the device total, once, at the wave's exit
+// (hm_collect's hits, hm_verify's bad records).
+DEV void wave_total(uint64_t* total, uint64_t count) {
+    if (count && __lane_id() == 0)
+        __hip_atomic_fetch_add(total, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---------------------------------------------------------------------------
+// Task ids of a persistent launch (seg_walk.cpp guided_tasks): ids below nbig
+// are whole units, each later unit is kSplit ids, one part each (the guided
+// tail).  `task` is parts [part, part_end) of the kSplit parts of `unit`: all
+// of them for a whole unit (false), one for a split unit (true).
+// ---------------------------------------------------------------------------
+DEV bool guided_split(uint32_t task, uint32_t nbig, uint32_t& unit, uint32_t& part,
+                      uint32_t& part_end) {
+    unit = task;
+    part = 0;
+    part_end = kSplit;
+    const bool split = task >= nbig;
+    if (split) {
+        const uint32_t k = task - nbig;
+        const uint32_t u = k / kSplit;
+        unit = nbig + u;
+        part = k - u * kSplit;
+        part_end = part + 1;
+    }
+    return split;
+}
+
+// Tiled launch: a unit is one lane chunk of one tile, a part one tens digit
+// of its loop, t1 in [t1_begin, t1_end).
+static_assert(kSplit == 10, "a part of a tiled unit is one tens digit");
+struct TiledTask {
+    uint32_t tile, chunk, t1_begin, t1_end;
+};
+DEV TiledTask tiled_decode(const TiledArgs& A, uint32_t task) {
+    // declared in this order: hipcc numbers the task loop's registers by it,
+    // and the tiled kernels' text is held equal to what it was before the
+    // decoders were shared.  Any order is as correct: this one only made
+    // the sharing checkable byte for byte and may be dropped later
+    uint32_t t1_end, t1_begin, unit;
+    guided_split(task, A.nbig, unit, t1_begin, t1_end);
+    const uint32_t tile = unit / A.tpt;
+    return {tile, unit - tile * A.tpt, t1_begin, t1_end};
+}
+
+// Chained launch: a unit is one loop chunk (tch loop values, the last one
+// ending at nloop) of one lane chunk of one tile, a part a kSplit-th of it,
+// rounded up; t in [t_begin, t_end).  per_tile = A.tpt * A.ntc, formed once
+// by the caller before its task loop.
+struct ChainedTask {
+    uint32_t tile, chunk, t_begin, t_end;
+};
+DEV ChainedTask chained_decode(const ChainedArgs& A, uint32_t per_tile, uint32_t task) {
+    uint32_t unit, part, part_end, nparts = 1;
+    if (guided_split(task, A.nbig, unit, part, part_end)) nparts = kSplit;
+    const uint32_t tile = unit / per_tile;
+    const uint32_t rem = unit - tile * per_tile;
+    const uint32_t chunk = rem / A.ntc;
+    const uint32_t tc = rem - chunk * A.ntc;
+    const uint32_t piece = (A.tch + nparts - 1) / nparts;
+    const uint32_t t_begin = tc * A.tch + part * piece;
+    uint32_t t_end = tc * A.tch + A.tch;
+    if (t_end > A.nloop) t_end = A.nloop;
+    if (t_end > t_begin + piece) t_end = t_begin + piece;
+    return {tile, chunk, t_begin, t_end};
+}
+
+// Every tiled layout the planner can pick (plan.cpp layout): one tail block
+// with W1 = 1..13, or W1 = 13..15 followed by a constant trailer block, each
+// without and with a straddling tens digit.  X(W1, STRADDLE, TRAILER); the
+// kernel instantiations and the fused kernel's switch all expand this list.
+#define HM_TILED_LAYOUT_S(X, W, T) X(W, false, T) X(W, true, T)
+#define HM_FOR_EACH_TILED_LAYOUT(X)                                              \
+    HM_TILED_LAYOUT_S(X, 1, false) HM_TILED_LAYOUT_S(X, 2, false)                \
+    HM_TILED_LAYOUT_S(X, 3, false) HM_TILED_LAYOUT_S(X, 4, false)                \
+    HM_TILED_LAYOUT_S(X, 5, false) HM_TILED_LAYOUT_S(X, 6, false)                \
+    HM_TILED_LAYOUT_S(X, 7, false) HM_TILED_LAYOUT_S(X, 8, false)                \
+    HM_TILED_LAYOUT_S(X, 9, false) HM_TILED_LAYOUT_S(X, 10, false)               \
+    HM_TILED_LAYOUT_S(X, 11, false) HM_TILED_LAYOUT_S(X, 12, false)              \
+    HM_TILED_LAYOUT_S(X, 13, false) HM_TILED_LAYOUT_S(X, 13, true)               \
+    HM_TILED_LAYOUT_S(X, 14, true) HM_TILED_LAYOUT_S(X, 15, true)
+
+// Launch bounds of the tiled kernels of every family.
+#ifndef HM_TILED_WAVES_PER_EU
+#define HM_TILED_WAVES_PER_EU 0
+#endif
+#if HM_TILED_WAVES_PER_EU > 0
+#define HM_TILED_BOUNDS __launch_bounds__(kBlock, HM_TILED_WAVES_PER_EU)
+#else
+#define HM_TILED_BOUNDS __launch_bounds__(kBlock)
+#endif
 
 // Workgroup-level task dispenser (round 5; the per-segment kernels and,
 // with kFusedLds, the fused one).  A wave draws a ticket from an

@@ -297,4 +297,32 @@ DEV void build_tail(uint32_t w[32], const uint32_t* pw, uint32_t r, uint32_t d, 
     }
 }
 
+// Hash(msg, n) of one nonce of d digits, every tail block built and
+// compressed per lane from the midstate `mid` (the generic scan kernels, the
+// fused kernel's generic tasks and the list kernel; hm_find_generic_kernel and
+// hm_collect_generic_kernel keep their own copies of this text and say why):
+// the key is (h0 << 32) | h1.  nb = 1 or 2 tail blocks; the second is
+// compressed only where nb == 2 (a scalar branch when nb is wave-uniform, the
+// exec mask otherwise).
+DEV void hash_nonce(const uint32_t* __restrict__ pw, uint32_t r, uint32_t d, uint32_t nb,
+                    uint64_t total_bits, const uint32_t* __restrict__ mid, uint64_t n,
+                    uint32_t& h0, uint32_t& h1) {
+    uint32_t w[32];
+    build_tail(w, pw, r, d, 0, n, nb, total_bits);
+    uint32_t st[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) st[j] = mid[j];
+    uint32_t m[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) m[j] = w[j];
+    d_compress(st, m);
+    if (nb == 2) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) m[j] = w[16 + j];
+        d_compress(st, m);
+    }
+    h0 = st[0];
+    h1 = st[1];
+}
+
 }  // namespace hm

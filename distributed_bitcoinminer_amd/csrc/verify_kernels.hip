@@ -69,6 +69,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "scan_tasks.hpp"
 #include "sha256_defs.hpp"
 #include "sha_device.hpp"
 
@@ -92,21 +93,9 @@ DEV uint32_t dec_digits(uint64_t n) {
 // wave-uniform (an SGPR after uni()) and once with d per lane.
 DEV uint64_t hash_tail(const VerifyArgs& A, uint64_t n, uint32_t d) {
     const uint32_t nb = A.r + d + 9u <= 64u ? 1u : 2u;
-    uint32_t w[32];
-    build_tail(w, A.pw, A.r, d, 0, n, nb, A.bits0 + 8u * d);
-    uint32_t st[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) st[j] = A.mid[j];
-    uint32_t m[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) m[j] = w[j];
-    d_compress(st, m);
-    if (nb == 2u) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) m[j] = w[16 + j];
-        d_compress(st, m);
-    }
-    return ((uint64_t)st[0] << 32) | st[1];
+    uint32_t h0, h1;
+    hash_nonce(A.pw, A.r, d, nb, A.bits0 + 8u * d, A.mid, n, h0, h1);
+    return ((uint64_t)h0 << 32) | h1;
 }
 
 template <bool VERIFY>
@@ -166,11 +155,7 @@ __global__ void __launch_bounds__(kBlock) hm_hash_list_kernel(const VerifyArgs A
             }
         }
     }
-    if constexpr (VERIFY) {
-        // the wave's count into the device total, once, at the wave's exit
-        if (count && lane == 0)
-            __hip_atomic_fetch_add(A.total, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if constexpr (VERIFY) wave_total(A.total, count);
 }
 
 template __global__ void hm_hash_list_kernel<false>(const VerifyArgs);
