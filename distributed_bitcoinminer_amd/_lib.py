@@ -40,6 +40,7 @@ HM_OPT_FUSED_TAIL = 14
 HM_OPT_TAIL_FUSED = 15
 HM_OPT_QUEUE_BATCH = 17
 HM_OPT_VERIFY_CHUNK = 19
+HM_OPT_FIND_WINDOW = 20
 HM_MERGE_NONE, HM_MERGE_HOST, HM_MERGE_RCCL = 0, 1, 2
 
 
@@ -86,6 +87,26 @@ class hm_find_stats(ctypes.Structure):
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class hm_find_request(ctypes.Structure):
+    """hm_find_request of include/hipminer.h (ABI 1.13)."""
+    _fields_ = [("msg", ctypes.c_char_p), ("len", ctypes.c_size_t),
+                ("lo", ctypes.c_uint64), ("hi", ctypes.c_uint64),
+                ("target", ctypes.c_uint64)]
+
+
+class hm_find_many_stats(ctypes.Structure):
+    """hm_find_many_stats of include/hipminer.h (ABI 1.13)."""
+    _fields_ = [("wall_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
+                ("nonces_enqueued", ctypes.c_uint64), ("tasks_total", ctypes.c_uint64),
+                ("tasks_run", ctypes.c_uint64), ("requests", ctypes.c_int32),
+                ("found", ctypes.c_int32), ("fused", ctypes.c_int32),
+                ("fallback", ctypes.c_int32), ("launches", ctypes.c_int32),
+                ("ndev", ctypes.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class hm_collect_stats(ctypes.Structure):
@@ -183,6 +204,18 @@ def load() -> ctypes.CDLL:
         lib.hm_find_stats_sized.restype = ctypes.c_int
         lib.hm_find_stats_sized.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_find_stats),
                                             ctypes.c_size_t]
+        lib.hm_find_many.restype = ctypes.c_int
+        lib.hm_find_many.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_find_request),
+                                     ctypes.c_int, ctypes.POINTER(hm_result),
+                                     ctypes.POINTER(ctypes.c_int)]
+        lib.hm_find_many_cpu.restype = ctypes.c_int
+        lib.hm_find_many_cpu.argtypes = [ctypes.POINTER(hm_find_request), ctypes.c_int,
+                                         ctypes.c_int, ctypes.POINTER(hm_result),
+                                         ctypes.POINTER(ctypes.c_int)]
+        lib.hm_find_many_stats_sized.restype = ctypes.c_int
+        lib.hm_find_many_stats_sized.argtypes = [ctypes.c_void_p,
+                                                 ctypes.POINTER(hm_find_many_stats),
+                                                 ctypes.c_size_t]
         lib.hm_collect.restype = ctypes.c_int
         lib.hm_collect.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint64,
                                    ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(hm_result),
@@ -316,6 +349,21 @@ class Context:
             raise HipMinerError(rc, "hm_find_stats_sized")
         return st.as_dict()
 
+    def find_many(self, requests):
+        """hm_find_many (ABI 1.13) over [(msg, lo, hi, target), ...]: for each
+        request what Context.find returns, (hash, nonce) or None; each
+        request's first 2^27 nonces run as one fused launch that exits early."""
+        return _find_many(lambda arr, n, outs, found: self._lib.hm_find_many(
+            self._h, arr, n, outs, found), "hm_find_many", requests)
+
+    def find_many_stats(self) -> dict:
+        """hm_find_many_stats_sized: work accounting of the last find_many on this context."""
+        st = hm_find_many_stats()
+        rc = self._lib.hm_find_many_stats_sized(self._h, ctypes.byref(st), ctypes.sizeof(st))
+        if rc != HM_OK:
+            raise HipMinerError(rc, "hm_find_many_stats_sized")
+        return st.as_dict()
+
     def collect(self, msg, lo: int, hi: int, target: int, cap: int):
         """hm_collect (ABI 1.11): (total, records).  total = the number of
         nonces in the inclusive [lo, hi] whose hash is below `target`, always
@@ -416,6 +464,29 @@ def find_cpu(msg, lo: int, hi: int, target: int, threads: int = 0):
     if rc != HM_OK:
         raise HipMinerError(rc, "hm_find_cpu")
     return (int(out.hash), int(out.nonce)) if found.value else None
+
+
+def _find_many(call, what: str, requests):
+    """Run a find_many entry point over [(msg, lo, hi, target), ...] and shape
+    its answers: a list of (hash, nonce) or None."""
+    reqs = list(requests)
+    n = len(reqs)
+    keep = [as_bytes(r[0]) for r in reqs]
+    arr = (hm_find_request * max(1, n))()
+    for i, ((_, lo, hi, target), m) in enumerate(zip(reqs, keep)):
+        arr[i] = hm_find_request(m, len(m), lo, hi, target)
+    outs = (hm_result * max(1, n))()
+    found = (ctypes.c_int * max(1, n))()
+    rc = call(arr, n, outs, found)
+    if rc != HM_OK:
+        raise HipMinerError(rc, what)
+    return [(int(outs[i].hash), int(outs[i].nonce)) if found[i] else None for i in range(n)]
+
+
+def find_many_cpu(requests, threads: int = 0):
+    """hm_find_many_cpu (ABI 1.13): Context.find_many's answers on the host's cores."""
+    return _find_many(lambda arr, n, outs, found: load().hm_find_many_cpu(
+        arr, n, threads, outs, found), "hm_find_many_cpu", requests)
 
 
 def _collect(call, what: str, msg, cap: int):

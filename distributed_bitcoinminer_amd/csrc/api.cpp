@@ -20,6 +20,8 @@
 //   (seg_walk.cpp); devices, streams and host waits are device.cpp's.
 //   hm_hash_many and hm_verify (ABI 1.12): verify.cpp, a list of arbitrary
 //   nonces through the one kernel of verify_kernels.hip.
+//   hm_find_many (ABI 1.13): find_many.cpp, one fused launch of
+//   fused_find_kernels.hip per request, hm_find's path for what is left.
 //   The scan kernels come from their own code object (scan_kernels.hip ->
 //   align_loops.py -> hipminer_scan.hsaco, embedded by scan_blob.S), loaded
 //   per device with hipModuleLoadData and launched with hipModuleLaunchKernel.
@@ -52,7 +54,8 @@ uint64_t hm_hash(const uint8_t* msg, size_t len, uint64_t nonce) {
 // 1.10: hm_find, hm_find_cpu, hm_find_stats_sized
 // 1.11: hm_collect, hm_collect_cpu, hm_collect_stats_sized
 // 1.12: hm_hash_many, hm_hash_many_cpu, hm_verify, hm_verify_cpu, hm_verify_stats_sized
-int hm_version(void) { return (1 << 16) | 12; }
+// 1.13: hm_find_many, hm_find_many_cpu, hm_find_many_stats_sized, HM_OPT_FIND_WINDOW
+int hm_version(void) { return (1 << 16) | 13; }
 
 // The digest of the sources this library was built from (build_id.py), kept
 // in the binary behind a tag so tools can read it without loading the library.
@@ -168,6 +171,10 @@ int hm_set_option(hm_ctx* ctx, int opt, int64_t value) {
                 return HM_ERR_INVALID;
             ctx->verify_chunk = (uint32_t)value;
             return HM_OK;
+        case HM_OPT_FIND_WINDOW:
+            if (value != 0 && (value < 64 || value > (int64_t)kFusedNonces)) return HM_ERR_INVALID;
+            ctx->find_window = (uint64_t)value;
+            return HM_OK;
         case HM_OPT_GRID_PER_CU:
             if (value < 0 || value > 32) return HM_ERR_INVALID;
             ctx->grid_per_cu = (int)value;
@@ -234,6 +241,35 @@ int hm_find_stats_sized(const hm_ctx* ctx, hm_find_stats* out, size_t size) {
     std::lock_guard<std::mutex> g(ctx->mu);
     if (!ctx->have_find_stats) return HM_ERR_INVALID;
     memcpy(out, &ctx->last_find, std::min(size, sizeof(hm_find_stats)));
+    return HM_OK;
+}
+
+int hm_find_many(hm_ctx* ctx, const hm_find_request* reqs, int n, hm_result* outs, int* found) {
+    if (!ctx || n < 0 || (n > 0 && (!reqs || !outs || !found))) return HM_ERR_INVALID;
+    for (int r = 0; r < n; ++r)
+        if (!reqs[r].msg && reqs[r].len) return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    std::vector<hm_result> res;
+    std::vector<int> hit;
+    int rc = guarded([&] {
+        res.resize((size_t)n);
+        hit.resize((size_t)n);
+        return find_many_locked(ctx, reqs, n, res.data(), hit.data());
+    });
+    if (rc) return rc;
+    // all n answers, or (on any failure above) none
+    for (int r = 0; r < n; ++r) {
+        outs[r] = res[r];
+        found[r] = hit[r];
+    }
+    return HM_OK;
+}
+
+int hm_find_many_stats_sized(const hm_ctx* ctx, hm_find_many_stats* out, size_t size) {
+    if (!ctx || !out || size < HM_FIND_MANY_STATS_SIZE_1_13) return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!ctx->have_find_many_stats) return HM_ERR_INVALID;
+    memcpy(out, &ctx->last_find_many, std::min(size, sizeof(hm_find_many_stats)));
     return HM_OK;
 }
 

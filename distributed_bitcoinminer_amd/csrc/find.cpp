@@ -48,12 +48,6 @@ struct FindDev {
     uint64_t word = ~0ull, run = 0;  // last readback
 };
 
-struct FindTally {
-    uint64_t nonces = 0, tasks = 0;
-    int launches = 0;
-    double kernel_ms = 0;
-};
-
 // Issue the device's next launch whose smallest nonce is <= best (the lowest
 // hit known; MaxUint64 = none), between two timing events, and count it.
 // *issued = false: nothing left to issue in this piece.  A pruned launch
@@ -130,17 +124,12 @@ int find_collect(hm_ctx* ctx, Device& dv, FindDev& fd, FindTally& tally) {
 
 }  // namespace
 
-// hm_find with ctx->mu held.
-int find_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
-                uint64_t target, hm_result* out, int* found) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const uint8_t* m;
-    size_t mlen;
-    int rc = begin_ranged_call(ctx, msg, len, lo, hi, t0, &m, &mlen);
-    if (rc) return rc;
+int find_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_t hi, uint64_t target,
+              FindTally* tally_out, hm_result* out, int* found) {
+    int rc;
     const int ndev = (int)ctx->devs.size();
-    FindTally tally;
-    uint64_t best = ~0ull, run = 0;
+    FindTally& tally = *tally_out;
+    uint64_t best = ~0ull;
     if (lo <= hi && target != 0) {
         const MsgPlan mp = plan_message(m, mlen);
         for (auto& dv : ctx->devs) {
@@ -184,7 +173,7 @@ int find_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64
                 }
             }
         }
-        for (const FindDev& fd : fds) run += fd.run;
+        for (const FindDev& fd : fds) tally.run += fd.run;
     }
     hm_result res{~0ull, 0};
     int hit = 0;
@@ -197,13 +186,31 @@ int find_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64
             hit = 1;
         }
     }
+    *out = res;
+    *found = hit;
+    return HM_OK;
+}
+
+// hm_find with ctx->mu held.
+int find_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
+                uint64_t target, hm_result* out, int* found) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint8_t* m;
+    size_t mlen;
+    int rc = begin_ranged_call(ctx, msg, len, lo, hi, t0, &m, &mlen);
+    if (rc) return rc;
+    FindTally tally;
+    hm_result res;
+    int hit = 0;
+    rc = find_core(ctx, m, mlen, lo, hi, target, &tally, &res, &hit);
+    if (rc) return rc;
     hm_find_stats st{};
     st.kernel_ms = tally.kernel_ms;
     st.nonces_enqueued = tally.nonces;
     st.tasks_total = tally.tasks;
-    st.tasks_run = run;
+    st.tasks_run = tally.run;
     st.launches = tally.launches;
-    st.ndev = ndev;
+    st.ndev = (int)ctx->devs.size();
     st.found = hit;
     st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
                      .count();

@@ -6,6 +6,7 @@
 //   seg_walk.cpp  one segment -> its sequence of launches (SegWalk), the argument fillers
 //   scan.cpp      hm_scan_many: batching, the fused launch, merge, stats
 //   find.cpp      hm_find
+//   find_many.cpp hm_find_many
 //   collect.cpp   hm_collect
 //   verify.cpp    hm_hash_many, hm_verify
 //   api.cpp       the extern "C" entry points and the debug exports
@@ -111,6 +112,8 @@ struct Device {
     uint64_t* result = nullptr;    // [kMaxBatch][2]
     uint64_t* gathered = nullptr;  // [ndev][kMaxBatch][2] (RCCL merge)
     uint64_t* find_ctl = nullptr;  // hm_find: [0] the stop word, [1] tasks run (kernels.hpp FindArgs)
+    // hm_find_many, made on first use: [kMaxBatch][2], request r's (stop word, tasks run)
+    uint64_t* find_many_ctl = nullptr;
     // hm_collect: [0] total, [1] slot cursor (kernels.hpp CollectArgs), and the record buffer of
     // collect_cap records, grown when a larger cap arrives (the old one joins `retired`)
     uint64_t* collect_ctl = nullptr;
@@ -165,6 +168,7 @@ struct hm_ctx {
     bool tail_fused = true;  // HM_OPT_TAIL_FUSED: a large request's tail segments in one fused launch
     int queue_batch = 0;     // HM_OPT_QUEUE_BATCH: 0 = auto, else tasks per queue atomic (4..32)
     uint32_t verify_chunk = 0;  // HM_OPT_VERIFY_CHUNK (test hook; 0 = kVerifyChunk)
+    uint64_t find_window = 0;   // HM_OPT_FIND_WINDOW (test hook; 0 = kFusedNonces)
     // host waits on GPU work while the call is still enqueuing (hm_stats.mid_call_syncs)
     bool enqueuing = false;
     int32_t mid_syncs = 0;
@@ -190,6 +194,8 @@ struct hm_ctx {
     hm_collect_stats last_collect{};
     bool have_verify_stats = false;  // and hm_hash_many / hm_verify
     hm_verify_stats last_verify{};
+    bool have_find_many_stats = false;  // and hm_find_many
+    hm_find_many_stats last_find_many{};
 };
 
 namespace hm {
@@ -382,10 +388,40 @@ int begin_ranged_call(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, 
 // a scan.  Returns rc.
 int drain_failed(hm_ctx* ctx, int rc);
 
+// ---- scan.cpp: the fused launch, shared with find_many.cpp ----
+bool fusible(const std::vector<SegPlan>& segs);
+// A fused launch as plan_fused lays it out.  The caller sets the outputs
+// (pa.result, pa.acc, pa.n_acc; fa.cand, fa.sums) and launches.
+struct FusedLaunch {
+    FusedPlanArgs pa;
+    FusedArgs fa;
+    int grid;
+    uint64_t nonces;
+    uint32_t comp_max;  // hm_stats: compressions per nonce, the largest of the segments
+    double comp_eff;    // and those executed, nonce-weighted
+};
+int plan_fused(hm_ctx* ctx, Device& dv, const MsgPlan& mp, const std::vector<SegPlan>& segs, int si,
+               uint32_t flags, FusedLaunch* out);
+
+// ---- find.cpp: hm_find without its opening and its stats, for hm_find_many's fallback ----
+struct FindTally {
+    uint64_t nonces = 0, tasks = 0, run = 0;
+    int launches = 0;
+    double kernel_ms = 0;
+};
+// The lowest nonce of [lo, hi] whose hash is below target, on stream 0 through
+// the per-segment find kernels: *res and *hit as hm_find returns them, the
+// work added to *tally.  The call's deadline is already set; on failure the
+// streams are drained (drain_failed).
+int find_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_t hi, uint64_t target,
+              FindTally* tally, hm_result* res, int* hit);
+
 // ---- scan.cpp, find.cpp, collect.cpp, verify.cpp: the entry points' bodies, ctx->mu held ----
 int scan_many_locked(hm_ctx* ctx, const hm_request* reqs, int n, hm_result* outs);
 int find_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
                 uint64_t target, hm_result* out, int* found);
+// hm_find_many: outs[i], found[i] for i < n, all written or (on failure) none.
+int find_many_locked(hm_ctx* ctx, const hm_find_request* reqs, int n, hm_result* outs, int* found);
 int collect_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
                    uint64_t target, size_t cap, std::vector<hm_result>* recs, uint64_t* total);
 // hm_hash_many (recs null: `list` holds n nonces, *out gets the n hashes) and

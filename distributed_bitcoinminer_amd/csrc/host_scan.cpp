@@ -1,7 +1,8 @@
-// host_scan.cpp -- hm_scan_cpu, hm_find_cpu, hm_collect_cpu, hm_hash_many_cpu
-// and hm_verify_cpu: the min-hash scan, the first-below-target search (ABI
-// 1.10), the all-below-target collection (ABI 1.11) and the recheck of a list
-// (ABI 1.12), on the host's cores.
+// host_scan.cpp -- hm_scan_cpu, hm_find_cpu, hm_find_many_cpu, hm_collect_cpu,
+// hm_hash_many_cpu and hm_verify_cpu: the min-hash scan, the first-below-target
+// search (ABI 1.10) and its batch form (ABI 1.13), the all-below-target
+// collection (ABI 1.11) and the recheck of a list (ABI 1.12), on the host's
+// cores.
 //
 // SURVEY §8(b)'s liveness path.  The reference miner always answers a
 // Request with a Result (cmu440/bitcoin/miner/miner.go:60-62); a GPU miner
@@ -418,6 +419,34 @@ extern "C" int hm_find_cpu(const uint8_t* msg, size_t len, uint64_t lo, uint64_t
         } else {
             *out = hm_result{~0ull, 0};
             *found = 0;
+        }
+        return HM_OK;
+    } catch (const std::bad_alloc&) {
+        return HM_ERR_NOMEM;
+    } catch (...) {
+        return HM_ERR_INTERNAL;
+    }
+}
+
+// hm_find_many's answers on the host (ABI 1.13): hm_find_cpu request by
+// request; all n outputs are written, or none.
+extern "C" int hm_find_many_cpu(const hm_find_request* reqs, int n, int threads, hm_result* outs,
+                                int* found) {
+    if (n < 0 || (n > 0 && (!reqs || !outs || !found))) return HM_ERR_INVALID;
+    for (int r = 0; r < n; ++r)
+        if (!reqs[r].msg && reqs[r].len) return HM_ERR_INVALID;
+    try {
+        std::vector<hm_result> res((size_t)n);
+        std::vector<int> hit((size_t)n);
+        for (int r = 0; r < n; ++r) {
+            const hm_find_request& q = reqs[r];
+            const int rc = hm_find_cpu(q.msg, q.msg ? q.len : 0, q.lo, q.hi, q.target, threads,
+                                       &res[r], &hit[r]);
+            if (rc) return rc;
+        }
+        for (int r = 0; r < n; ++r) {
+            outs[r] = res[r];
+            found[r] = hit[r];
         }
         return HM_OK;
     } catch (const std::bad_alloc&) {

@@ -237,6 +237,15 @@ struct FindGenericArgs {
     GenericArgs g;
     FindArgs f;
 };
+// hm_find_many (fused_find_kernels.hip): one request's window,
+// every segment in one launch.  `f.word` and `f.tasks_run` are the REQUEST's
+// pair, seeded (MaxUint64, 0) by the planner launch (FusedPlanArgs::result);
+// a.cand, a.sums, a.flags and a.trace are unused and f.launch_lo is not read
+// (the word is MaxUint64 when the launch starts).
+struct FusedFindArgs {
+    FusedArgs a;
+    FindArgs f;
+};
 
 // ---------------------------------------------------------------------------
 // hm_collect (collect_kernels.hip, DESIGN.md "All below target"): every nonce

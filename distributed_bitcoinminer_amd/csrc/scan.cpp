@@ -50,6 +50,8 @@ int enqueue_segment(hm_ctx* ctx, Device& dv, const MsgPlan& mp, const SegPlan& s
     return HM_OK;
 }
 
+}  // namespace
+
 // Fused launch (kernels.hpp, fused_kernels.hip): can all of a request's
 // segments run in one launch?  Up to kFusedNonces nonces and 20 segments;
 // tiled and generic segments always, chained ones with one table of f <= 4
@@ -69,47 +71,24 @@ bool fusible(const std::vector<SegPlan>& segs) {
     return n <= (long double)kFusedNonces && rows <= kFusedKwRows && tiles <= kMaxTilesPerLaunch;
 }
 
-// Per-task cost rank of a segment's layout in the fused launch: the queue
-// hands out the costly tasks first, so the launch ends on the cheapest ones.
-int fused_rank(const SegPlan& g) {
-    if (g.kind == HM_KIND_CHAINED) return 0;   // 64 lanes x up to 100 blocks
-    if (g.kind == HM_KIND_GENERIC) return 1;   // 640 nonces, full tail compressions
-    return g.trailer ? 2 : 3;                  // 640 nonces, 2 or 1 compressions
-}
-
-// Enqueue every segment of one request as ONE fused launch on stream si:
-// hm_fused_plan_kernel (records, tables, counter; and, when `seed_best`, the
-// (MaxUint64, 0) seed of *best and zeroed coverage sums) -> hm_fused_kernel
-// -> hm_fold_kernel into *best.  Tasks are ordered costliest layout first,
-// larger segments first.
-int enqueue_fused(hm_ctx* ctx, Device& dv, const MsgPlan& mp, std::vector<SegPlan> segs, int si,
-                  uint64_t* best, bool seed_best) {
-    hipStream_t st = dv.stream[si];
-    std::stable_sort(segs.begin(), segs.end(), [](const SegPlan& a, const SegPlan& b) {
-        if (fused_rank(a) != fused_rank(b)) return fused_rank(a) < fused_rank(b);
-        return a.hi - a.lo > b.hi - b.lo;
-    });
-    FusedPlanArgs pa;
+// What a fused launch of `segs`, in that task order, on stream si is: the
+// planner's and the kernel's argument blocks (segment descriptors, tasks,
+// guided tail, the counter's start), the grid and the stats figures.
+int plan_fused(hm_ctx* ctx, Device& dv, const MsgPlan& mp, const std::vector<SegPlan>& segs, int si,
+               uint32_t flags, FusedLaunch* out) {
+    FusedPlanArgs& pa = out->pa;
     memset(&pa, 0, sizeof pa);
-    FusedArgs fa;
+    FusedArgs& fa = out->fa;
     memset(&fa, 0, sizeof fa);
     pa.rec = dv.rec[si];
     pa.aux = dv.aux[si];
     pa.counter = dv.counter[si];
-    pa.result = seed_best ? best : nullptr;
-    // a lone request (seed_best) also zeroes every stream's coverage sums,
-    // which hm_scan_checked adds up; in a batch they were zeroed up front
-    // and hold the other requests' sums
-    pa.acc = ctx->csum && seed_best ? dv.acc : nullptr;
-    pa.n_acc = 2 * kStreams;
     pa.r = mp.r;
     memcpy(pa.pw, mp.pw, sizeof pa.pw);
     memcpy(pa.mid, mp.mid, sizeof pa.mid);
     fa.rec = dv.rec[si];
     fa.aux = dv.aux[si];
     fa.counter = dv.counter[si];
-    fa.cand = dv.cand[si];
-    fa.sums = ctx->csum ? dv.sums[si] : nullptr;
     fa.r = mp.r;
     memcpy(fa.pw, mp.pw, sizeof fa.pw);
     memcpy(fa.mid, mp.mid, sizeof fa.mid);
@@ -225,31 +204,73 @@ int enqueue_fused(hm_ctx* ctx, Device& dv, const MsgPlan& mp, std::vector<SegPla
     fa.nparts = nparts > 1 ? nparts : 1;
     fa.nseg = pa.nseg = (uint32_t)segs.size();
     pa.njobs = (uint32_t)jobs;
+    // small launches: few waves per SIMD keep a task short, so the launch's
+    // tail is short (kFusedPerCu = 3 workgroups per CU, profiles/r05/fused/)
+    out->grid = persistent_grid(ctx, dv, kFusedPerCu, ids);
+    fa.flags = flags;
+    // with static first tasks the queue starts past every wave slot
+    pa.counter0 = (flags & kFusedStaticFirst) ? (uint32_t)out->grid * (kBlock / kWaveSize) : 0;
+    out->nonces = nonces;
+    out->comp_max = comp_max;
+    out->comp_eff = comp_w / (double)nonces;
+    return HM_OK;
+}
+
+namespace {
+
+// Per-task cost rank of a segment's layout in the fused launch: the queue
+// hands out the costly tasks first, so the launch ends on the cheapest ones.
+int fused_rank(const SegPlan& g) {
+    if (g.kind == HM_KIND_CHAINED) return 0;   // 64 lanes x up to 100 blocks
+    if (g.kind == HM_KIND_GENERIC) return 1;   // 640 nonces, full tail compressions
+    return g.trailer ? 2 : 3;                  // 640 nonces, 2 or 1 compressions
+}
+
+// Enqueue every segment of one request as ONE fused launch on stream si:
+// hm_fused_plan_kernel (records, tables, counter; and, when `seed_best`, the
+// (MaxUint64, 0) seed of *best and zeroed coverage sums) -> hm_fused_kernel
+// -> hm_fold_kernel into *best.  Tasks are ordered costliest layout first,
+// larger segments first.
+int enqueue_fused(hm_ctx* ctx, Device& dv, const MsgPlan& mp, std::vector<SegPlan> segs, int si,
+                  uint64_t* best, bool seed_best) {
+    hipStream_t st = dv.stream[si];
+    std::stable_sort(segs.begin(), segs.end(), [](const SegPlan& a, const SegPlan& b) {
+        if (fused_rank(a) != fused_rank(b)) return fused_rank(a) < fused_rank(b);
+        return a.hi - a.lo > b.hi - b.lo;
+    });
+    FusedLaunch fl;
+    int rc = plan_fused(ctx, dv, mp, segs, si, ctx->fused_flags, &fl);
+    if (rc) return rc;
+    FusedPlanArgs& pa = fl.pa;
+    FusedArgs& fa = fl.fa;
+    pa.result = seed_best ? best : nullptr;
+    // a lone request (seed_best) also zeroes every stream's coverage sums,
+    // which hm_scan_checked adds up; in a batch they were zeroed up front
+    // and hold the other requests' sums
+    pa.acc = ctx->csum && seed_best ? dv.acc : nullptr;
+    pa.n_acc = 2 * kStreams;
+    fa.cand = dv.cand[si];
+    fa.sums = ctx->csum ? dv.sums[si] : nullptr;
     const Device::Fn* fn = nullptr;
     // built once: a fused request's whole enqueue is ~10 us
     static const KernelName names[2] = {kernel_name(Family::Scan, HM_KIND_FUSED, nullptr),
                                         kernel_name(Family::ScanCsum, HM_KIND_FUSED, nullptr)};
     const KernelName& name = names[ctx->csum ? 1 : 0];
-    int rc = scan_fn(dv, name.symbol, &fn);
+    rc = scan_fn(dv, name.symbol, &fn);
     if (rc) return rc;
-    // small launches: few waves per SIMD keep a task short, so the launch's
-    // tail is short (kFusedPerCu = 3 workgroups per CU, profiles/r05/fused/)
-    const int grid = persistent_grid(ctx, dv, kFusedPerCu, ids);
-    fa.flags = ctx->fused_flags;
-    // with static first tasks the queue starts past every wave slot
-    pa.counter0 = (fa.flags & kFusedStaticFirst) ? (uint32_t)grid * (kBlock / kWaveSize) : 0;
+    const int grid = fl.grid;
     HIPCHK(launch_fused_plan(pa, st));
     Launch L;
     rc = next_event(dv, &L.start);
     if (rc) return rc;
     rc = next_event(dv, &L.stop);
     if (rc) return rc;
-    L.nonces = nonces;
+    L.nonces = fl.nonces;
     L.kind = HM_KIND_FUSED;
     snprintf(L.kernel, sizeof L.kernel, "%s", name.display.c_str());
     L.grid = grid;
-    L.compressions = comp_max;
-    L.comp_eff = comp_w / (double)nonces;
+    L.compressions = fl.comp_max;
+    L.comp_eff = fl.comp_eff;
     HIPCHK(hipEventRecord(L.start, st));
     rc = launch_scan(*fn, fa, grid, st);
     if (rc) return rc;

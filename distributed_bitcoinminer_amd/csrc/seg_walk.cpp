@@ -13,9 +13,13 @@ KernelName kernel_name(Family family, int kind, const SegPlan* s) {
     const int li = kind == HM_KIND_TILED ? 1 : kind == HM_KIND_CHAINED ? 2 : kind == HM_KIND_FUSED ? 3 : 0;
     const char* pre = family == Family::Find ? "find_" : family == Family::Collect ? "collect_" : "";
     const char* arg_pre = family == Family::Find ? "Find" : family == Family::Collect ? "Collect" : "";
-    const std::string fn = std::string("hm_") + pre + layouts[li] +
-                           (family == Family::ScanCsum ? "_csum" : "") + "_kernel";
-    const std::string arg = std::string(arg_pre) + args[li];
+    std::string fn = std::string("hm_") + pre + layouts[li] +
+                     (family == Family::ScanCsum ? "_csum" : "") + "_kernel";
+    std::string arg = std::string(arg_pre) + args[li];
+    if (family == Family::Find && kind == HM_KIND_FUSED) {  // fused_find_kernels.hip
+        fn = "hm_fused_find_kernel";
+        arg = "FusedFindArgs";
+    }
     char targs[48] = "", shown[48] = "";
     if (kind == HM_KIND_TILED) {  // hm_*tiled*_kernel<W1, STRADDLE, TRAILER>
         snprintf(targs, sizeof targs, "ILi%dELb%dELb%dEEEv", s->W1, s->straddle ? 1 : 0,

@@ -356,6 +356,76 @@ typedef struct hm_find_stats {
  * HM_ERR_INVALID before the first one. */
 int hm_find_stats_sized(const hm_ctx *ctx, hm_find_stats *out, size_t size);
 
+/* ABI 1.13: a batch of finds.  outs[i], found[i] = what hm_find(reqs[i])
+ * returns, for i < n, bit for bit: the LOWEST qualifying nonce under strict
+ * '<', (UINT64_MAX, 0) with found = 0 otherwise; target = 0 and lo > hi never
+ * hit; hi may be UINT64_MAX, and nonce UINT64_MAX can be an answer.
+ *
+ * At ordinary targets the first hit lies a few million nonces in, and hm_find
+ * is bound by its launches and host round trips, not by hashing.  Here each
+ * request's WINDOW -- its first 2^27 nonces, [lo, min(hi, lo + 2^27 - 1)] --
+ * runs as ONE fused launch with hm_find's early exit (one stop word per
+ * request), request r whole on device r mod ndev, round-robin
+ * over that device's streams (HM_OPT_STREAMS, as hm_scan_many), and every
+ * request of a chunk of 64 is enqueued on every device before the host waits
+ * on any.  Of the window, the longest ascending run of digit segments that a
+ * fused launch can hold is fused (all of it, but for chained layouts of more
+ * than four final-block digits).  A request with no hit there whose range goes
+ * on continues from the first nonce not fused through hm_find's per-segment
+ * path, one request after another.  The host recomputes each hit's hash.
+ *
+ * n == 0 is HM_OK and enqueues nothing.  HM_ERR_INVALID: n < 0; n > 0 with
+ * reqs, outs or found NULL; any request with msg == NULL and len > 0
+ * (msg == NULL with len == 0 is the empty message).  Outputs are written only
+ * on HM_OK, and all n are written or none.  An abandoned context returns
+ * HM_ERR_TIMEOUT.  HM_OPT_DEADLINE_MS applies to the whole call (auto: 2 s +
+ * 8 x the sum of what hm_find's auto rule models for each request).
+ * HM_OPT_FORCE_GENERIC and HM_OPT_GRID_PER_CU are honoured as the fused scan
+ * launch honours them; HM_OPT_FUSED = 0 sends every request down the
+ * per-segment path (the in-library A/B); the RCCL option does not apply.  Each
+ * device keeps 64 word pairs, made on first use and kept until hm_close.  The
+ * call changes nothing that hm_scan_stats*, hm_find_stats_sized,
+ * hm_collect_stats_sized or hm_verify_stats_sized report. */
+typedef struct hm_find_request {
+    const uint8_t *msg;   /* borrowed for the call; may be NULL when len == 0 */
+    size_t len;
+    uint64_t lo, hi;      /* inclusive */
+    uint64_t target;
+} hm_find_request;
+
+int hm_find_many(hm_ctx *ctx, const hm_find_request *reqs, int n, hm_result *outs, int *found);
+
+/* The same answers on the host's cores, no GPU: hm_find_cpu request by
+ * request (`threads` as there), under the same contract. */
+int hm_find_many_cpu(const hm_find_request *reqs, int n, int threads, hm_result *outs,
+                     int *found);
+
+/* Work accounting of the most recent successful hm_find_many on a context.
+ * The struct only grows at its end. */
+typedef struct hm_find_many_stats {
+    double wall_ms;           /* host wall time of the call                      */
+    double kernel_ms;         /* summed HIP-event time of the fused find launches
+                                 and of any fallback launches                    */
+    uint64_t nonces_enqueued; /* as in hm_find_stats, summed over the batch      */
+    uint64_t tasks_total;     /*   (a fused launch: its task ids)                */
+    uint64_t tasks_run;
+    int32_t requests;         /* n                                               */
+    int32_t found;            /* requests with a hit                             */
+    int32_t fused;            /* requests answered by their fused launch alone: a
+                                 hit in it, or it covered [lo, hi]               */
+    int32_t fallback;         /* requests that needed the per-segment path.  A
+                                 request that enqueues nothing (lo > hi,
+                                 target = 0) counts in neither                   */
+    int32_t launches;         /* fused find launches plus fallback launches      */
+    int32_t ndev;             /* devices of the context                          */
+} hm_find_many_stats;
+#define HM_FIND_MANY_STATS_SIZE_1_13 64 /* ABI 1.13 */
+
+/* Writes at most `size` bytes (pass sizeof the struct as the caller compiled
+ * it; >= HM_FIND_MANY_STATS_SIZE_1_13) of the last successful hm_find_many's
+ * stats; HM_ERR_INVALID before the first one. */
+int hm_find_many_stats_sized(const hm_ctx *ctx, hm_find_many_stats *out, size_t size);
+
 /* ABI 1.11: share collection.  The result of
  *   for n = lo .. hi (inclusive): if Hash(msg, n) < target: emit (Hash, n)
  * *total = the number of such n, always exact (the whole range is always

@@ -55,6 +55,10 @@ extern "C" {
                                   per chunk and device of the list calls, so a
                                   list of a few hundred records crosses chunk
                                   boundaries (ids 16 and 18 stay retired)      */
+#define HM_OPT_FIND_WINDOW 20   /* test hook (64..2^27; 0 = default 2^27; ABI
+                                  1.13): nonces of a request that hm_find_many
+                                  runs as its fused launch, so a test can put
+                                  the window's end anywhere                    */
 
 /* The embedded scan code object: *p = its first byte, returns its size.
  * bench.py hashes these bytes to match a PMC summary to the build that runs. */
