@@ -41,6 +41,7 @@ HM_OPT_TAIL_FUSED = 15
 HM_OPT_QUEUE_BATCH = 17
 HM_OPT_VERIFY_CHUNK = 19
 HM_OPT_FIND_WINDOW = 20
+HM_OPT_VERIFY_JOBS = 21
 HM_MERGE_NONE, HM_MERGE_HOST, HM_MERGE_RCCL = 0, 1, 2
 
 
@@ -127,6 +128,31 @@ class hm_verify_stats(ctypes.Structure):
                 ("bad", ctypes.c_uint64), ("launches", ctypes.c_int32),
                 ("ndev", ctypes.c_int32), ("overflow", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class hm_verify_request(ctypes.Structure):
+    """hm_verify_request of include/hipminer.h (ABI 1.14)."""
+    _fields_ = [("msg", ctypes.c_char_p), ("len", ctypes.c_size_t),
+                ("recs", ctypes.POINTER(hm_result)), ("n", ctypes.c_size_t),
+                ("target", ctypes.c_uint64)]
+
+
+class hm_bad_ref(ctypes.Structure):
+    """hm_bad_ref of include/hipminer.h (ABI 1.14)."""
+    _fields_ = [("request", ctypes.c_uint64), ("index", ctypes.c_uint64)]
+
+
+class hm_verify_many_stats(ctypes.Structure):
+    """hm_verify_many_stats of include/hipminer.h (ABI 1.14)."""
+    _fields_ = [("wall_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
+                ("copy_ms", ctypes.c_double), ("records", ctypes.c_uint64),
+                ("bad", ctypes.c_uint64), ("tasks", ctypes.c_uint64),
+                ("requests", ctypes.c_int32), ("launches", ctypes.c_int32),
+                ("copies", ctypes.c_int32), ("ndev", ctypes.c_int32),
+                ("overflow", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
@@ -244,6 +270,18 @@ def load() -> ctypes.CDLL:
         lib.hm_verify_stats_sized.restype = ctypes.c_int
         lib.hm_verify_stats_sized.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_verify_stats),
                                               ctypes.c_size_t]
+        lib.hm_verify_many.restype = ctypes.c_int
+        lib.hm_verify_many.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_verify_request),
+                                       ctypes.c_int, u64p, ctypes.POINTER(hm_bad_ref),
+                                       ctypes.c_size_t, u64p]
+        lib.hm_verify_many_cpu.restype = ctypes.c_int
+        lib.hm_verify_many_cpu.argtypes = [ctypes.POINTER(hm_verify_request), ctypes.c_int,
+                                           ctypes.c_int, u64p, ctypes.POINTER(hm_bad_ref),
+                                           ctypes.c_size_t, u64p]
+        lib.hm_verify_many_stats_sized.restype = ctypes.c_int
+        lib.hm_verify_many_stats_sized.argtypes = [ctypes.c_void_p,
+                                                   ctypes.POINTER(hm_verify_many_stats),
+                                                   ctypes.c_size_t]
         lib.hm_debug_auto_deadline_ms.restype = ctypes.c_double
         lib.hm_debug_auto_deadline_ms.argtypes = [u8p, ctypes.c_size_t, ctypes.c_uint64,
                                                   ctypes.c_uint64, ctypes.c_int]
@@ -408,6 +446,23 @@ class Context:
             raise HipMinerError(rc, "hm_verify_stats_sized")
         return st.as_dict()
 
+    def verify_many(self, requests, cap: int):
+        """hm_verify_many (ABI 1.14) over [(msg, records, target), ...]:
+        (bad, per-request counts, refs).  bad and the counts (a list of ints,
+        what Context.verify returns for each request) are always exact; refs =
+        the bad (request, index) pairs, ascending, as a list of tuples when
+        bad <= cap, and None when bad > cap.  `records` as Context.verify's."""
+        return _verify_many(lambda arr, n, per, refs, c, bad: self._lib.hm_verify_many(
+            self._h, arr, n, per, refs, c, bad), "hm_verify_many", requests, cap)
+
+    def verify_many_stats(self) -> dict:
+        """hm_verify_many_stats_sized: accounting of the last verify_many."""
+        st = hm_verify_many_stats()
+        rc = self._lib.hm_verify_many_stats_sized(self._h, ctypes.byref(st), ctypes.sizeof(st))
+        if rc != HM_OK:
+            raise HipMinerError(rc, "hm_verify_many_stats_sized")
+        return st.as_dict()
+
     def streams_made(self, device_index: int = 0) -> int:
         """HIP streams (hardware queues) the context has made on its
         device_index-th device (debug export; ABI 1.8 makes them on first use)."""
@@ -545,6 +600,51 @@ def _verify(call, what: str, msg, records, cap: int):
         raise HipMinerError(rc, what)
     b = int(bad.value)
     return (b, None) if b > cap else (b, idx[:b].copy() if cap else np.empty(0, np.uint64))
+
+
+def verify_requests(requests):
+    """[(msg, records, target), ...] as an hm_verify_request array: (array, n,
+    the objects the array borrows from -- keep them alive for the call)."""
+    import numpy as np
+    reqs = list(requests)
+    n = len(reqs)
+    arr = (hm_verify_request * max(1, n))()
+    keep = []
+    for i, (msg, records, target) in enumerate(reqs):
+        m = as_bytes(msg)
+        r = np.ascontiguousarray(records, dtype=np.uint64).reshape(-1, 2)
+        keep.append((m, r))
+        arr[i] = hm_verify_request(m, len(m),
+                                   r.ctypes.data_as(ctypes.POINTER(hm_result)) if r.shape[0]
+                                   else None, r.shape[0], target)
+    return arr, n, keep
+
+
+def _verify_many(call, what: str, requests, cap: int):
+    import numpy as np
+    arr, n, keep = verify_requests(requests)
+    per = np.zeros(max(1, n), dtype=np.uint64)
+    refs = (hm_bad_ref * cap)() if cap else None
+    bad = ctypes.c_uint64(0)
+    rc = call(arr, n, per.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), refs, cap,
+              ctypes.byref(bad))
+    del keep
+    if rc != HM_OK:
+        raise HipMinerError(rc, what)
+    b = int(bad.value)
+    counts = [int(x) for x in per[:n]]
+    if b > cap:
+        return b, counts, None
+    if b == 0:
+        return 0, counts, []
+    words = struct.unpack_from(f"={2 * b}Q", refs)
+    return b, counts, list(zip(words[0::2], words[1::2]))
+
+
+def verify_many_cpu(requests, cap: int, threads: int = 0):
+    """hm_verify_many_cpu (ABI 1.14): Context.verify_many's answer on the host's cores."""
+    return _verify_many(lambda arr, n, per, refs, c, bad: load().hm_verify_many_cpu(
+        arr, n, threads, per, refs, c, bad), "hm_verify_many_cpu", requests, cap)
 
 
 def hash_many_cpu(msg, nonces, threads: int = 0):

@@ -22,6 +22,8 @@
 //   nonces through the one kernel of verify_kernels.hip.
 //   hm_find_many (ABI 1.13): find_many.cpp, one fused launch of
 //   fused_find_kernels.hip per request, hm_find's path for what is left.
+//   hm_verify_many (ABI 1.14): verify_many.cpp, the lists of many messages
+//   through the job kernel of verify_many_kernels.hip.
 //   The scan kernels come from their own code object (scan_kernels.hip ->
 //   align_loops.py -> hipminer_scan.hsaco, embedded by scan_blob.S), loaded
 //   per device with hipModuleLoadData and launched with hipModuleLaunchKernel.
@@ -55,7 +57,8 @@ uint64_t hm_hash(const uint8_t* msg, size_t len, uint64_t nonce) {
 // 1.11: hm_collect, hm_collect_cpu, hm_collect_stats_sized
 // 1.12: hm_hash_many, hm_hash_many_cpu, hm_verify, hm_verify_cpu, hm_verify_stats_sized
 // 1.13: hm_find_many, hm_find_many_cpu, hm_find_many_stats_sized, HM_OPT_FIND_WINDOW
-int hm_version(void) { return (1 << 16) | 13; }
+// 1.14: hm_verify_many, hm_verify_many_cpu, hm_verify_many_stats_sized, HM_OPT_VERIFY_JOBS
+int hm_version(void) { return (1 << 16) | 14; }
 
 // The digest of the sources this library was built from (build_id.py), kept
 // in the binary behind a tag so tools can read it without loading the library.
@@ -170,6 +173,10 @@ int hm_set_option(hm_ctx* ctx, int opt, int64_t value) {
             if (value < 0 || value > (int64_t)kVerifyChunk || value % kWaveSize != 0)
                 return HM_ERR_INVALID;
             ctx->verify_chunk = (uint32_t)value;
+            return HM_OK;
+        case HM_OPT_VERIFY_JOBS:
+            if (value < 0 || value > (int64_t)kVerifyJobsMax) return HM_ERR_INVALID;
+            ctx->verify_jobs = (uint32_t)value;
             return HM_OK;
         case HM_OPT_FIND_WINDOW:
             if (value != 0 && (value < 64 || value > (int64_t)kFusedNonces)) return HM_ERR_INVALID;
@@ -333,6 +340,34 @@ int hm_verify_stats_sized(const hm_ctx* ctx, hm_verify_stats* out, size_t size) 
     std::lock_guard<std::mutex> g(ctx->mu);
     if (!ctx->have_verify_stats) return HM_ERR_INVALID;
     memcpy(out, &ctx->last_verify, std::min(size, sizeof(hm_verify_stats)));
+    return HM_OK;
+}
+
+int hm_verify_many(hm_ctx* ctx, const hm_verify_request* reqs, int nreq, uint64_t* bad_per_req,
+                   hm_bad_ref* refs, size_t cap, uint64_t* bad) {
+    if (!ctx || nreq < 0 || (nreq > 0 && (!reqs || !bad_per_req)) || !bad ||
+        cap > HM_VERIFY_CAP_MAX || (cap && !refs))
+        return HM_ERR_INVALID;
+    for (int r = 0; r < nreq; ++r)
+        if ((!reqs[r].msg && reqs[r].len) || (!reqs[r].recs && reqs[r].n)) return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    std::vector<uint64_t> per;
+    std::vector<hm_bad_ref> out;
+    uint64_t sum = 0;
+    int rc = guarded([&] { return verify_many_locked(ctx, reqs, nreq, cap, &per, &out, &sum); });
+    if (rc) return rc;
+    // every count, and the refs when they fit; on any failure above, nothing
+    for (int r = 0; r < nreq; ++r) bad_per_req[r] = per[r];
+    if (sum <= cap && sum) memcpy(refs, out.data(), (size_t)sum * sizeof(hm_bad_ref));
+    *bad = sum;
+    return HM_OK;
+}
+
+int hm_verify_many_stats_sized(const hm_ctx* ctx, hm_verify_many_stats* out, size_t size) {
+    if (!ctx || !out || size < HM_VERIFY_MANY_STATS_SIZE_1_14) return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!ctx->have_verify_many_stats) return HM_ERR_INVALID;
+    memcpy(out, &ctx->last_verify_many, std::min(size, sizeof(hm_verify_many_stats)));
     return HM_OK;
 }
 

@@ -109,6 +109,13 @@ void device_free(Device& dv) {
     if (dv.verify_ctl) (void)hipFree(dv.verify_ctl);
     if (dv.verify_in) (void)hipFree(dv.verify_in);
     if (dv.verify_idx) (void)hipFree(dv.verify_idx);
+    if (dv.vm_blob) (void)hipFree(dv.vm_blob);
+    if (dv.vm_ctl) (void)hipFree(dv.vm_ctl);
+    if (dv.vm_refs) (void)hipFree(dv.vm_refs);
+    for (uint64_t* p : dv.vm_stage)
+        if (p) (void)hipHostFree(p);
+    for (void* p : dv.retired_host) (void)hipHostFree(p);
+    dv.retired_host.clear();
     if (dv.host_out) (void)hipHostFree(dv.host_out);
     dv.ordinal = -1;
 }
@@ -184,6 +191,30 @@ int host_wait(hm_ctx* ctx, hipStream_t st) {
         const hipError_t e = hipStreamQuery(st);
         if (e == hipSuccess) return HM_OK;
         if (e != hipErrorNotReady) return hip_fail(e, "hipStreamQuery");
+        const auto now = clk::now();
+        if (now >= ctx->deadline_at) {
+            ctx->abandoned = true;
+            if (debug_on())
+                fprintf(stderr, "hipminer: scan deadline of %.1f ms passed: context abandoned\n",
+                        ctx->deadline_ms);
+            return HM_ERR_TIMEOUT;
+        }
+        if (now - t0 < std::chrono::milliseconds(2)) std::this_thread::yield();
+        else std::this_thread::sleep_for(std::chrono::microseconds(100));
+    }
+}
+int host_wait(hm_ctx* ctx, hipEvent_t ev) {
+    if (ctx->enqueuing) ++ctx->mid_syncs;
+    if (!ctx->has_deadline) {
+        HIPCHK(hipEventSynchronize(ev));
+        return HM_OK;
+    }
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    for (;;) {
+        const hipError_t e = hipEventQuery(ev);
+        if (e == hipSuccess) return HM_OK;
+        if (e != hipErrorNotReady) return hip_fail(e, "hipEventQuery");
         const auto now = clk::now();
         if (now >= ctx->deadline_at) {
             ctx->abandoned = true;
@@ -275,7 +306,7 @@ void call_deadline(hm_ctx* ctx, const hm_request* reqs, int n,
     set_deadline(ctx, ctx->deadline_opt < 0 ? auto_deadline_ms(ctx, reqs, n) : 0.0, t0);
 }
 
-// hm_hash_many and hm_verify have no range to model: auto is the same floor
+// hm_hash_many, hm_verify and hm_verify_many have no range to model: auto is the same floor
 // plus the same slack times a wall time per list element: the median wall of
 // hm_verify over 4,192,403 records of the 120-B message, the slower of the two
 // messages measured (1.6845 ms; profiles/verify/verify_rate.jsonl part (a)).

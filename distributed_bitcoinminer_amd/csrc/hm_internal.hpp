@@ -9,6 +9,7 @@
 //   find_many.cpp hm_find_many
 //   collect.cpp   hm_collect
 //   verify.cpp    hm_hash_many, hm_verify
+//   verify_many.cpp hm_verify_many
 //   api.cpp       the extern "C" entry points and the debug exports
 #pragma once
 #include <hip/hip_runtime.h>
@@ -127,6 +128,19 @@ struct Device {
     size_t verify_in_bytes = 0;
     uint64_t* verify_idx = nullptr;
     size_t verify_idx_cap = 0;
+    // hm_verify_many, all made on first use and grown like collect_buf: two pinned staging slots
+    // (a launch's [job table | task_job | records], used alternately), the device blob they are
+    // copied to, the control words ([0] slot cursor, [1 + j] the bad count of the call's job j on
+    // this device) and the buffer of vm_refs_cap 16-byte refs
+    uint64_t* vm_stage[2] = {};
+    size_t vm_stage_bytes[2] = {};
+    std::vector<void*> retired_host;  // pinned slots replaced by larger ones, freed at hm_close
+    uint64_t* vm_blob = nullptr;
+    size_t vm_blob_bytes = 0;
+    uint64_t* vm_ctl = nullptr;
+    size_t vm_ctl_words = 0;
+    uint64_t* vm_refs = nullptr;
+    size_t vm_refs_cap = 0;
     hm_result* host_out = nullptr; // pinned, fine-grained [kMaxBatch]: the 16-B readback slots
     hipEvent_t join[kStreams] = {};
     hipEvent_t gate = nullptr;     // stream 0 reached its last dominant segment
@@ -168,6 +182,7 @@ struct hm_ctx {
     bool tail_fused = true;  // HM_OPT_TAIL_FUSED: a large request's tail segments in one fused launch
     int queue_batch = 0;     // HM_OPT_QUEUE_BATCH: 0 = auto, else tasks per queue atomic (4..32)
     uint32_t verify_chunk = 0;  // HM_OPT_VERIFY_CHUNK (test hook; 0 = kVerifyChunk)
+    uint32_t verify_jobs = 0;   // HM_OPT_VERIFY_JOBS (test hook; 0 = kVerifyJobsMax)
     uint64_t find_window = 0;   // HM_OPT_FIND_WINDOW (test hook; 0 = kFusedNonces)
     // host waits on GPU work while the call is still enqueuing (hm_stats.mid_call_syncs)
     bool enqueuing = false;
@@ -196,6 +211,8 @@ struct hm_ctx {
     hm_verify_stats last_verify{};
     bool have_find_many_stats = false;  // and hm_find_many
     hm_find_many_stats last_find_many{};
+    bool have_verify_many_stats = false;  // and hm_verify_many
+    hm_verify_many_stats last_verify_many{};
 };
 
 namespace hm {
@@ -207,6 +224,8 @@ bool distinct_ordinals(const hm_ctx* ctx);
 int next_event(Device& dv, hipEvent_t* ev);
 int make_streams(Device& dv, int n);
 int host_wait(hm_ctx* ctx, hipStream_t st);
+// The same wait for one event of a stream (hm_verify_many's staging slots).
+int host_wait(hm_ctx* ctx, hipEvent_t ev);
 int host_read(hm_ctx* ctx, void* dst, const void* src, size_t n);
 int kw_table_rows(hm_ctx* ctx, Device& dv, int si, uint64_t rows);
 double modelled_deadline_ms(const hm_request* reqs, int n, bool force_generic, int table_digits,
@@ -381,7 +400,7 @@ private:
 // abandoned context.
 int begin_ranged_call(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
                       std::chrono::steady_clock::time_point t0, const uint8_t** m, size_t* mlen);
-// A find, collect, hash_many or verify that fails part-way with rc leaves nothing behind: every
+// A find, collect, hash_many, verify or verify_many that fails part-way with rc leaves nothing behind: every
 // device's stream 0 is waited for (launches still queued use its record,
 // table, counter and control buffers) and its timing events are free again.
 // After a timeout the context is abandoned and nothing is waited for, as for
@@ -430,5 +449,12 @@ int collect_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uin
 int list_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, const uint64_t* nonces,
                 const hm_result* recs, size_t n, uint64_t target, size_t cap,
                 std::vector<uint64_t>* out, uint64_t* bad);
+// Make *buf hold `want` units of `unit` bytes of device memory (*have: what it
+// holds now); a larger one replaces it and the old one is retired (verify.cpp).
+int grow_buffer(Device& dv, uint64_t** buf, size_t* have, size_t want, size_t most, size_t unit);
+// hm_verify_many: per[i] for i < nreq, *refs (the bad (request, index) pairs,
+// ascending, when *bad <= cap; empty otherwise) and *bad.
+int verify_many_locked(hm_ctx* ctx, const hm_verify_request* reqs, int nreq, size_t cap,
+                       std::vector<uint64_t>* per, std::vector<hm_bad_ref>* refs, uint64_t* bad);
 
 }  // namespace hm

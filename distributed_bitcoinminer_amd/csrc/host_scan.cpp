@@ -1,8 +1,8 @@
 // host_scan.cpp -- hm_scan_cpu, hm_find_cpu, hm_find_many_cpu, hm_collect_cpu,
-// hm_hash_many_cpu and hm_verify_cpu: the min-hash scan, the first-below-target
-// search (ABI 1.10) and its batch form (ABI 1.13), the all-below-target
-// collection (ABI 1.11) and the recheck of a list (ABI 1.12), on the host's
-// cores.
+// hm_hash_many_cpu, hm_verify_cpu and hm_verify_many_cpu: the min-hash scan, the
+// first-below-target search (ABI 1.10) and its batch form (ABI 1.13), the
+// all-below-target collection (ABI 1.11), the recheck of a list (ABI 1.12) and
+// of the lists of many messages (ABI 1.14), on the host's cores.
 //
 // SURVEY §8(b)'s liveness path.  The reference miner always answers a
 // Request with a Result (cmu440/bitcoin/miner/miner.go:60-62); a GPU miner
@@ -27,6 +27,7 @@
 #include <algorithm>
 #include <atomic>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #if defined(__x86_64__)
@@ -276,6 +277,44 @@ void verify_part(const MsgPlan& mp, const hm_result* recs, size_t a, size_t b, u
             const bool bad = recs[i].hash >= target ||
                              recs[i].hash != hash_from_mid(mp, recs[i].nonce, compress);
             if (bad && ++out->count <= cap) out->idx.push_back(i);
+        }
+    } catch (...) {
+        out->failed = true;
+    }
+}
+
+// hm_verify_many_cpu's share of one thread: positions [a, b) of the flattened
+// record sequence (start[i]: request i's first position).  Per request it
+// touches, the bad count of its part of that request, in order; the bad
+// (request, index) pairs ascending, stored as VerifyPart stores its indices.
+struct VerifyManyPart {
+    std::vector<std::pair<size_t, uint64_t>> counts;  // (request, bad records of it in this part)
+    std::vector<hm_bad_ref> refs;
+    uint64_t count = 0;
+    bool failed = false;  // out of memory
+};
+
+void verify_many_part(const hm_verify_request* reqs, const std::vector<MsgPlan>& plans,
+                      const std::vector<uint64_t>& start, size_t a, size_t b, size_t cap,
+                      CompressFn compress, VerifyManyPart* out) {
+    try {
+        size_t r = (size_t)(std::upper_bound(start.begin(), start.end(), (uint64_t)a) -
+                            start.begin()) - 1;
+        size_t pos = a;
+        while (pos < b) {
+            while (start[r + 1] <= pos) ++r;  // past requests without records too
+            const size_t end = std::min<size_t>((size_t)start[r + 1], b);
+            const hm_verify_request& q = reqs[r];
+            uint64_t bad_here = 0;
+            for (size_t i = pos - (size_t)start[r]; i < end - (size_t)start[r]; ++i) {
+                const bool bad = q.recs[i].hash >= q.target ||
+                                 q.recs[i].hash != hash_from_mid(plans[r], q.recs[i].nonce, compress);
+                if (!bad) continue;
+                ++bad_here;
+                if (++out->count <= cap) out->refs.push_back(hm_bad_ref{r, i});
+            }
+            out->counts.emplace_back(r, bad_here);
+            pos = end;
         }
     } catch (...) {
         out->failed = true;
@@ -579,6 +618,66 @@ extern "C" int hm_verify_cpu(const uint8_t* msg, size_t len, const hm_result* re
             for (const VerifyPart& p : part) {
                 if (!p.idx.empty()) memcpy(bad_idx + at, p.idx.data(), p.idx.size() * sizeof(uint64_t));
                 at += p.idx.size();
+            }
+        }
+        *bad = sum;
+        return HM_OK;
+    } catch (const std::bad_alloc&) {
+        return HM_ERR_NOMEM;
+    } catch (...) {
+        return HM_ERR_INTERNAL;
+    }
+}
+
+extern "C" int hm_verify_many_cpu(const hm_verify_request* reqs, int nreq, int threads,
+                                  uint64_t* bad_per_req, hm_bad_ref* refs, size_t cap,
+                                  uint64_t* bad) {
+    using namespace hm;
+    if (nreq < 0 || (nreq > 0 && (!reqs || !bad_per_req)) || !bad || cap > HM_VERIFY_CAP_MAX ||
+        (cap && !refs))
+        return HM_ERR_INVALID;
+    for (int r = 0; r < nreq; ++r)
+        if ((!reqs[r].msg && reqs[r].len) || (!reqs[r].recs && reqs[r].n)) return HM_ERR_INVALID;
+    try {
+        // the flattened sequence: request i holds positions [start[i], start[i + 1])
+        std::vector<uint64_t> start((size_t)nreq + 1, 0);
+        for (int i = 0; i < nreq; ++i) {
+            if (reqs[i].n > SIZE_MAX - start[i]) return HM_ERR_INVALID;
+            start[i + 1] = start[i] + reqs[i].n;
+        }
+        const size_t total = (size_t)start[nreq];
+        std::vector<uint64_t> per((size_t)nreq, 0);
+        std::vector<VerifyManyPart> part;
+        uint64_t sum = 0;
+        if (total > 0) {
+            static const uint8_t empty = 0;
+            std::vector<MsgPlan> plans((size_t)nreq);
+            for (int i = 0; i < nreq; ++i)
+                if (reqs[i].n)
+                    plans[i] = plan_message(reqs[i].msg ? reqs[i].msg : &empty,
+                                            reqs[i].msg ? reqs[i].len : 0);
+            const CompressFn compress = pick_compress();
+            const int rc = over_list(
+                total, threads, [&](unsigned parts) { part.resize(parts); },
+                [&](unsigned t, size_t a, size_t b) {
+                    verify_many_part(reqs, plans, start, a, b, cap, compress, &part[t]);
+                });
+            if (rc) return rc;
+            for (const VerifyManyPart& p : part) {
+                if (p.failed) return HM_ERR_NOMEM;
+                for (const auto& c : p.counts) per[c.first] += c.second;
+                sum += p.count;  // <= total
+            }
+        }
+        // all outputs from here on, none before
+        for (int i = 0; i < nreq; ++i) bad_per_req[i] = per[i];
+        if (sum <= cap) {
+            // the parts ascend and each is ascending: so is the concatenation
+            size_t at = 0;
+            for (const VerifyManyPart& p : part) {
+                if (!p.refs.empty())
+                    memcpy(refs + at, p.refs.data(), p.refs.size() * sizeof(hm_bad_ref));
+                at += p.refs.size();
             }
         }
         *bad = sum;

@@ -300,6 +300,39 @@ struct VerifyArgs {
     uint32_t mid[8];      // midstate after the constant blocks
 };
 
+// ---------------------------------------------------------------------------
+// hm_verify_many (verify_many_kernels.hip): the record lists of
+// many messages in one launch.  A JOB is one request, or the piece of one that
+// a launch holds; a TASK is 64 consecutive records of one job.  The host
+// writes the job table, the task -> job table and the packed records of a
+// launch into one blob (verify_many.cpp); the kernel reads a task's job
+// record wave-uniformly and then runs the list kernel's body with it.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kVerifyJobsMax = 4096;  // jobs per launch: the table stays under 1 MiB
+struct VerifyJob {
+    uint64_t target;   // a record with hash >= target is bad
+    uint64_t bits0;    // (len + 1) * 8
+    uint64_t index0;   // index, inside its request, of the job's first record
+    uint64_t request;  // the request the job belongs to
+    uint32_t first;    // element offset of the job's records in the launch's record buffer
+    uint32_t n;        // records of the job (>= 1)
+    uint32_t task0;    // the job's first task id: task t holds records (t - task0) * 64 ..
+    uint32_t r;        // prefix-remainder bytes in front of the digits
+    uint32_t pw[16];   // prefix remainder, big-endian words, zero padded
+    uint32_t mid[8];   // midstate after the constant blocks
+};
+static_assert(sizeof(VerifyJob) == 144, "the host packs VerifyJob records into a byte blob");
+struct VerifyJobsArgs {
+    const VerifyJob* jobs;     // the launch's job table
+    const uint32_t* task_job;  // [ntasks]: the job of each task
+    const uint64_t* recs;      // the launch's records, 2 x u64 (hash, nonce) each
+    uint64_t* bad;             // [jobs of the launch]: += a task's bad records
+    uint64_t* cursor;          // slot reservations (cap > 0 only)
+    uint64_t* refs;            // cap slots of 2 x u64 (request, index); null when cap == 0
+    uint32_t ntasks;
+    uint32_t cap;              // <= HM_VERIFY_CAP_MAX
+};
+
 // Launchers of the auxiliary kernels (kernels.hip; return hipError_t of the
 // launch).  The scan kernels (scan_kernels.hip: hm_tiled_kernel<W1,
 // STRADDLE, TRAILER>, hm_chained_kernel, hm_generic_kernel and their

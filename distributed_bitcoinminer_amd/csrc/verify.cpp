@@ -33,6 +33,15 @@ const char* list_kernel_symbol(bool verify) {
                   : "_ZN2hm19hm_hash_list_kernelILb0EEEvNS_10VerifyArgsE";
 }
 
+// One device's share of a call: list elements [lo, hi).
+struct ListDev {
+    size_t lo = 0, hi = 0;
+    std::vector<hipEvent_t> ev;  // per chunk: before the copy in, the launch, after it[, after the copy out]
+    int launches = 0;
+};
+
+}  // namespace
+
 // Make *buf hold `want` units of `unit` bytes (*have: what it holds now).  A
 // larger one replaces it -- at least twice the old size, at most `most` units
 // -- and the old one is kept until hm_close, as collect.cpp's record buffer.
@@ -49,15 +58,6 @@ int grow_buffer(Device& dv, uint64_t** buf, size_t* have, size_t want, size_t mo
     *have = size;
     return HM_OK;
 }
-
-// One device's share of a call: list elements [lo, hi).
-struct ListDev {
-    size_t lo = 0, hi = 0;
-    std::vector<hipEvent_t> ev;  // per chunk: before the copy in, the launch, after it[, after the copy out]
-    int launches = 0;
-};
-
-}  // namespace
 
 int list_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, const uint64_t* nonces,
                 const hm_result* recs, size_t n, uint64_t target, size_t cap,

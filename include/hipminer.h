@@ -561,6 +561,102 @@ typedef struct hm_verify_stats {
  * HM_ERR_INVALID before the first one. */
 int hm_verify_stats_sized(const hm_ctx *ctx, hm_verify_stats *out, size_t size);
 
+/* ABI 1.14: recheck the lists of many jobs.  hm_verify checks one message and
+ * one list per blocking call; a pool sets its share target so that each
+ * returned list is small, and serves many clients, so it holds many messages
+ * at once.  hm_verify_many takes a batch of (message, list, target) requests
+ * and answers all of them from as few launches as hold them: the message
+ * changes INSIDE a launch.
+ *
+ *   bad_per_req[i] = the *bad that hm_verify(reqs[i]) returns, always exact.
+ *   *bad           = the sum of the per-request counts.
+ * Record k of request i is BAD iff
+ *       recs[k].hash != Hash(msg_i, recs[k].nonce)  or  recs[k].hash >= target_i
+ * -- 1.12's rule verbatim, target = 0 (every record bad) and target =
+ * UINT64_MAX (the hash alone, but a hash of UINT64_MAX is bad) included.
+ *
+ * The size-query idiom, with ONE cap for the whole call:
+ *   *bad <= cap: refs[0 .. *bad) holds every bad (request, index), ASCENDING by
+ *                request and then by index (the index counts inside the
+ *                request's list); nothing at or beyond refs[*bad] is touched.
+ *   *bad >  cap: refs is not written at all.  The counts still are.
+ *   cap == 0 with refs == NULL gives the pure counts.
+ *
+ * Requests may repeat a message, a list or a pointer; each is answered on its
+ * own.  A request with n == 0 is legal and counts 0.  nreq == 0 is HM_OK with
+ * *bad = 0 and enqueues nothing.  HM_ERR_INVALID: nreq < 0; nreq > 0 with
+ * reqs or bad_per_req NULL; bad == NULL; cap > HM_VERIFY_CAP_MAX; cap > 0 with
+ * refs == NULL; any request with msg == NULL and len > 0 (msg == NULL with
+ * len == 0 is the empty message) or recs == NULL and n > 0.  Outputs are
+ * written only on HM_OK, all of them or none.  An abandoned context returns
+ * HM_ERR_TIMEOUT.  HM_OPT_DEADLINE_MS applies to the whole call (auto:
+ * hm_verify's rule over the summed record count); no other option does.
+ *
+ * Stream 0 only; no stream is created.  The concatenation of all requests'
+ * records is cut contiguously across the context's devices in even shares by
+ * record count (a cut may fall inside a request).  Each share is walked in
+ * order and packed into launches: a launch closes when it holds 2^22 records
+ * or 4096 jobs (a job: one request, or the piece of one that the launch
+ * holds; a request is cut where a launch fills).  Per launch the host packs
+ * the job table and the records into a pinned staging slot of the context and
+ * issues ONE copy and ONE kernel launch; all devices' work is enqueued before
+ * the host waits on any (beyond two launches per device it first waits for a
+ * staging slot's copy), then the host sums the pieces' counts per request and
+ * sorts the refs.  The caller's memory is neither registered nor altered.
+ * Each device keeps two staging slots, a device copy of one, its count words
+ * and a buffer of `cap` refs, made on first use, grown when needed and kept
+ * until the context is closed.  The call changes nothing that hm_scan_stats*,
+ * hm_find_stats_sized, hm_find_many_stats_sized, hm_collect_stats_sized or
+ * hm_verify_stats_sized report.
+ *
+ * The packing pass is a host copy of every record: a caller with ONE large
+ * list keeps hm_verify, which copies straight from the caller's memory. */
+typedef struct hm_verify_request {
+    const uint8_t *msg;     /* borrowed for the call; may be NULL when len == 0 */
+    size_t len;
+    const hm_result *recs;  /* borrowed for the call; may be NULL when n == 0 */
+    size_t n;
+    uint64_t target;
+} hm_verify_request;
+
+typedef struct hm_bad_ref {
+    uint64_t request;  /* position of the request in reqs     */
+    uint64_t index;    /* position of the bad record in its list */
+} hm_bad_ref;          /* 16 bytes */
+
+int hm_verify_many(hm_ctx *ctx, const hm_verify_request *reqs, int nreq,
+                   uint64_t *bad_per_req, hm_bad_ref *refs, size_t cap, uint64_t *bad);
+
+/* The same answers on the host's cores, no GPU, under the same contract
+ * (`threads` and the compression as hm_verify_cpu's).  The flattened record
+ * sequence is split over the threads; their counts and refs are concatenated
+ * in order. */
+int hm_verify_many_cpu(const hm_verify_request *reqs, int nreq, int threads,
+                       uint64_t *bad_per_req, hm_bad_ref *refs, size_t cap, uint64_t *bad);
+
+/* Accounting of the most recent successful hm_verify_many on a context.  The
+ * struct only grows at its end. */
+typedef struct hm_verify_many_stats {
+    double wall_ms;    /* host wall time of the call                             */
+    double kernel_ms;  /* summed HIP-event time of its launches                  */
+    double copy_ms;    /* summed HIP-event time of its copies to the device      */
+    uint64_t records;  /* summed record count of the requests                    */
+    uint64_t bad;      /* the call's *bad                                        */
+    uint64_t tasks;    /* tasks (64 records of one job) of those launches        */
+    int32_t requests;  /* nreq                                                   */
+    int32_t launches;  /* kernel launches issued                                 */
+    int32_t copies;    /* host-to-device copies issued (one per launch)          */
+    int32_t ndev;      /* devices of the context                                 */
+    int32_t overflow;  /* 1: *bad > cap, refs was not written; else 0            */
+    int32_t reserved;
+} hm_verify_many_stats;
+#define HM_VERIFY_MANY_STATS_SIZE_1_14 72 /* ABI 1.14 */
+
+/* Writes at most `size` bytes (pass sizeof the struct as the caller compiled
+ * it; >= HM_VERIFY_MANY_STATS_SIZE_1_14) of the last successful
+ * hm_verify_many's stats; HM_ERR_INVALID before the first one. */
+int hm_verify_many_stats_sized(const hm_ctx *ctx, hm_verify_many_stats *out, size_t size);
+
 int hm_set_option(hm_ctx *ctx, int opt, int64_t value);
 
 const char *hm_strerror(int rc);

@@ -59,6 +59,11 @@ extern "C" {
                                   1.13): nonces of a request that hm_find_many
                                   runs as its fused launch, so a test can put
                                   the window's end anywhere                    */
+#define HM_OPT_VERIFY_JOBS 21   /* test hook (1..4096; 0 = default 4096; ABI
+                                  1.14): jobs one hm_verify_many launch holds,
+                                  so a batch of a few requests crosses launch
+                                  boundaries; with HM_OPT_VERIFY_CHUNK, which
+                                  that call honours as its records bound       */
 
 /* The embedded scan code object: *p = its first byte, returns its size.
  * bench.py hashes these bytes to match a PMC summary to the build that runs. */
