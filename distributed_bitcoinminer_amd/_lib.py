@@ -42,6 +42,7 @@ HM_OPT_QUEUE_BATCH = 17
 HM_OPT_VERIFY_CHUNK = 19
 HM_OPT_FIND_WINDOW = 20
 HM_OPT_VERIFY_JOBS = 21
+HM_OPT_COLLECT_WINDOW = 22
 HM_MERGE_NONE, HM_MERGE_HOST, HM_MERGE_RCCL = 0, 1, 2
 
 
@@ -156,6 +157,26 @@ class hm_verify_many_stats(ctypes.Structure):
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class hm_collect_request(ctypes.Structure):
+    """hm_collect_request of include/hipminer.h (ABI 1.15)."""
+    _fields_ = [("msg", ctypes.c_char_p), ("len", ctypes.c_size_t),
+                ("lo", ctypes.c_uint64), ("hi", ctypes.c_uint64),
+                ("target", ctypes.c_uint64)]
+
+
+class hm_collect_many_stats(ctypes.Structure):
+    """hm_collect_many_stats of include/hipminer.h (ABI 1.15)."""
+    _fields_ = [("wall_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
+                ("nonces", ctypes.c_uint64), ("total", ctypes.c_uint64),
+                ("tasks", ctypes.c_uint64), ("requests", ctypes.c_int32),
+                ("fused", ctypes.c_int32), ("fallback", ctypes.c_int32),
+                ("launches", ctypes.c_int32), ("ndev", ctypes.c_int32),
+                ("overflow", ctypes.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 HM_COLLECT_CAP_MAX = 1 << 24
@@ -282,6 +303,18 @@ def load() -> ctypes.CDLL:
         lib.hm_verify_many_stats_sized.argtypes = [ctypes.c_void_p,
                                                    ctypes.POINTER(hm_verify_many_stats),
                                                    ctypes.c_size_t]
+        lib.hm_collect_many.restype = ctypes.c_int
+        lib.hm_collect_many.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_collect_request),
+                                        ctypes.c_int, u64p, ctypes.POINTER(hm_result),
+                                        ctypes.c_size_t, u64p]
+        lib.hm_collect_many_cpu.restype = ctypes.c_int
+        lib.hm_collect_many_cpu.argtypes = [ctypes.POINTER(hm_collect_request), ctypes.c_int,
+                                            ctypes.c_int, u64p, ctypes.POINTER(hm_result),
+                                            ctypes.c_size_t, u64p]
+        lib.hm_collect_many_stats_sized.restype = ctypes.c_int
+        lib.hm_collect_many_stats_sized.argtypes = [ctypes.c_void_p,
+                                                    ctypes.POINTER(hm_collect_many_stats),
+                                                    ctypes.c_size_t]
         lib.hm_debug_auto_deadline_ms.restype = ctypes.c_double
         lib.hm_debug_auto_deadline_ms.argtypes = [u8p, ctypes.c_size_t, ctypes.c_uint64,
                                                   ctypes.c_uint64, ctypes.c_int]
@@ -420,6 +453,29 @@ class Context:
         rc = self._lib.hm_collect_stats_sized(self._h, ctypes.byref(st), ctypes.sizeof(st))
         if rc != HM_OK:
             raise HipMinerError(rc, "hm_collect_stats_sized")
+        return st.as_dict()
+
+    def collect_many(self, requests, cap: int):
+        """hm_collect_many (ABI 1.15) over [(msg, lo, hi, target), ...]:
+        (total, per-request totals, records).  The totals (a list of ints, what
+        Context.collect returns for each request) and their sum are always
+        exact; records = for each request the list of its (hash, nonce),
+        ascending by nonce, when total <= cap, and None when total > cap.  A
+        msg of None is the empty message passed as a NULL pointer."""
+        return _collect_many(lambda arr, n, per, out, c, tot: self._lib.hm_collect_many(
+            self._h, arr, n, per, out, c, tot), "hm_collect_many", requests, cap)
+
+    def count_many(self, requests) -> list:
+        """hm_collect_many with no buffer: for each request how many nonces of
+        its range hash below its target."""
+        return self.collect_many(requests, 0)[1]
+
+    def collect_many_stats(self) -> dict:
+        """hm_collect_many_stats_sized: work accounting of the last collect_many."""
+        st = hm_collect_many_stats()
+        rc = self._lib.hm_collect_many_stats_sized(self._h, ctypes.byref(st), ctypes.sizeof(st))
+        if rc != HM_OK:
+            raise HipMinerError(rc, "hm_collect_many_stats_sized")
         return st.as_dict()
 
     def hash_many(self, msg, nonces):
@@ -571,6 +627,49 @@ def collect_cpu(msg, lo: int, hi: int, target: int, cap: int, threads: int = 0):
 def count_cpu(msg, lo: int, hi: int, target: int, threads: int = 0) -> int:
     """hm_collect_cpu with no buffer: Context.count's answer on the host's cores."""
     return collect_cpu(msg, lo, hi, target, 0, threads)[0]
+
+
+def collect_requests(requests):
+    """[(msg, lo, hi, target), ...] as an hm_collect_request array: (array, n,
+    the byte strings the array borrows -- keep them alive for the call).  A
+    msg of None becomes a NULL pointer with len 0."""
+    reqs = list(requests)
+    n = len(reqs)
+    keep = [None if r[0] is None else as_bytes(r[0]) for r in reqs]
+    arr = (hm_collect_request * max(1, n))()
+    for i, ((_, lo, hi, target), m) in enumerate(zip(reqs, keep)):
+        arr[i] = hm_collect_request(m, len(m) if m is not None else 0, lo, hi, target)
+    return arr, n, keep
+
+
+def _collect_many(call, what: str, requests, cap: int):
+    """Run a collect_many entry point with one buffer of `cap` records (none
+    for cap = 0) and shape its answer: (total, [totals], [[(hash, nonce), ...]
+    per request] or None)."""
+    arr, n, keep = collect_requests(requests)
+    per = (ctypes.c_uint64 * max(1, n))()
+    buf = (hm_result * cap)() if cap else None
+    total = ctypes.c_uint64(0)
+    rc = call(arr, n, per, buf, cap, ctypes.byref(total))
+    del keep
+    if rc != HM_OK:
+        raise HipMinerError(rc, what)
+    t = int(total.value)
+    totals = [int(per[i]) for i in range(n)]
+    if t > cap:
+        return t, totals, None
+    words = struct.unpack_from(f"={2 * t}Q", buf) if t else ()
+    recs, at = [], 0
+    for k in totals:
+        recs.append(list(zip(words[2 * at:2 * (at + k):2], words[2 * at + 1:2 * (at + k):2])))
+        at += k
+    return t, totals, recs
+
+
+def collect_many_cpu(requests, cap: int, threads: int = 0):
+    """hm_collect_many_cpu (ABI 1.15): Context.collect_many's answer on the host's cores."""
+    return _collect_many(lambda arr, n, per, out, c, tot: load().hm_collect_many_cpu(
+        arr, n, threads, per, out, c, tot), "hm_collect_many_cpu", requests, cap)
 
 
 def _hash_many(call, what: str, msg, nonces):

@@ -24,6 +24,8 @@
 //   fused_find_kernels.hip per request, hm_find's path for what is left.
 //   hm_verify_many (ABI 1.14): verify_many.cpp, the lists of many messages
 //   through the job kernel of verify_many_kernels.hip.
+//   hm_collect_many (ABI 1.15): collect_many.cpp, one fused launch of
+//   fused_collect_kernels.hip per request, hm_collect's path for the rest.
 //   The scan kernels come from their own code object (scan_kernels.hip ->
 //   align_loops.py -> hipminer_scan.hsaco, embedded by scan_blob.S), loaded
 //   per device with hipModuleLoadData and launched with hipModuleLaunchKernel.
@@ -58,7 +60,8 @@ uint64_t hm_hash(const uint8_t* msg, size_t len, uint64_t nonce) {
 // 1.12: hm_hash_many, hm_hash_many_cpu, hm_verify, hm_verify_cpu, hm_verify_stats_sized
 // 1.13: hm_find_many, hm_find_many_cpu, hm_find_many_stats_sized, HM_OPT_FIND_WINDOW
 // 1.14: hm_verify_many, hm_verify_many_cpu, hm_verify_many_stats_sized, HM_OPT_VERIFY_JOBS
-int hm_version(void) { return (1 << 16) | 14; }
+// 1.15: hm_collect_many, hm_collect_many_cpu, hm_collect_many_stats_sized, HM_OPT_COLLECT_WINDOW
+int hm_version(void) { return (1 << 16) | 15; }
 
 // The digest of the sources this library was built from (build_id.py), kept
 // in the binary behind a tag so tools can read it without loading the library.
@@ -182,6 +185,10 @@ int hm_set_option(hm_ctx* ctx, int opt, int64_t value) {
             if (value != 0 && (value < 64 || value > (int64_t)kFusedNonces)) return HM_ERR_INVALID;
             ctx->find_window = (uint64_t)value;
             return HM_OK;
+        case HM_OPT_COLLECT_WINDOW:
+            if (value != 0 && (value < 64 || value > (int64_t)kFusedNonces)) return HM_ERR_INVALID;
+            ctx->collect_window = (uint64_t)value;
+            return HM_OK;
         case HM_OPT_GRID_PER_CU:
             if (value < 0 || value > 32) return HM_ERR_INVALID;
             ctx->grid_per_cu = (int)value;
@@ -301,6 +308,34 @@ int hm_collect_stats_sized(const hm_ctx* ctx, hm_collect_stats* out, size_t size
     std::lock_guard<std::mutex> g(ctx->mu);
     if (!ctx->have_collect_stats) return HM_ERR_INVALID;
     memcpy(out, &ctx->last_collect, std::min(size, sizeof(hm_collect_stats)));
+    return HM_OK;
+}
+
+int hm_collect_many(hm_ctx* ctx, const hm_collect_request* reqs, int n, uint64_t* totals,
+                    hm_result* out, size_t cap, uint64_t* total) {
+    if (!ctx || n < 0 || (n > 0 && (!reqs || !totals)) || !total || cap > HM_COLLECT_CAP_MAX ||
+        (cap && !out))
+        return HM_ERR_INVALID;
+    for (int r = 0; r < n; ++r)
+        if (!reqs[r].msg && reqs[r].len) return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    std::vector<uint64_t> per;
+    std::vector<hm_result> recs;
+    uint64_t sum = 0;
+    int rc = guarded([&] { return collect_many_locked(ctx, reqs, n, cap, &per, &recs, &sum); });
+    if (rc) return rc;
+    // every total, and the records when they fit; on any failure above, nothing
+    for (int r = 0; r < n; ++r) totals[r] = per[r];
+    if (sum <= cap && sum) memcpy(out, recs.data(), (size_t)sum * sizeof(hm_result));
+    *total = sum;
+    return HM_OK;
+}
+
+int hm_collect_many_stats_sized(const hm_ctx* ctx, hm_collect_many_stats* out, size_t size) {
+    if (!ctx || !out || size < HM_COLLECT_MANY_STATS_SIZE_1_15) return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!ctx->have_collect_many_stats) return HM_ERR_INVALID;
+    memcpy(out, &ctx->last_collect_many, std::min(size, sizeof(hm_collect_many_stats)));
     return HM_OK;
 }
 

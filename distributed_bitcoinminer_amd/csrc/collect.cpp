@@ -27,6 +27,8 @@ struct CollectDev {
     int launches = 0;
 };
 
+}  // namespace
+
 // Make dv's record buffer hold `cap` records.  A larger one replaces it (at
 // least twice the old size, so all the buffers a device retires together are
 // smaller than its current one); the old buffer is kept until hm_close, as
@@ -44,6 +46,8 @@ int collect_buffer(Device& dv, size_t cap) {
     dv.collect_cap = want;
     return HM_OK;
 }
+
+namespace {
 
 // Enqueue every launch of segment s on dv's stream 0 (the device's first
 // launch of the call after its `first` timing event).
@@ -72,15 +76,13 @@ int collect_segment(hm_ctx* ctx, Device& dv, CollectDev& cd, const MsgPlan& mp, 
 
 }  // namespace
 
-// hm_collect with ctx->mu held.  *recs: the records, ascending by nonce, when
-// *total <= cap; empty otherwise.
-int collect_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
-                   uint64_t target, size_t cap, std::vector<hm_result>* recs, uint64_t* total) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const uint8_t* m;
-    size_t mlen;
-    int rc = begin_ranged_call(ctx, msg, len, lo, hi, t0, &m, &mlen);
-    if (rc) return rc;
+// hm_collect between its opening and its stats record (hm_collect_many's
+// fallback runs it too).  *recs: the records, ascending by nonce, when *total
+// <= cap; empty otherwise.
+int collect_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_t hi,
+                 uint64_t target, size_t cap, CollectTally* tally, std::vector<hm_result>* recs,
+                 uint64_t* total) {
+    int rc;
     const int ndev = (int)ctx->devs.size();
     std::vector<CollectDev> cds(ndev);
     uint64_t sum = 0;
@@ -171,15 +173,34 @@ int collect_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uin
             }
         }
     }
-    hm_collect_stats st{};
-    st.kernel_ms = kernel_ms;
-    st.total = sum;
-    st.ndev = ndev;
-    st.overflow = sum > cap ? 1 : 0;
+    tally->kernel_ms += kernel_ms;
     for (const CollectDev& cd : cds) {
-        st.nonces += cd.nonces;
-        st.launches += cd.launches;
+        tally->nonces += cd.nonces;
+        tally->launches += cd.launches;
     }
+    *total = sum;
+    return HM_OK;
+}
+
+// hm_collect with ctx->mu held.
+int collect_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
+                   uint64_t target, size_t cap, std::vector<hm_result>* recs, uint64_t* total) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint8_t* m;
+    size_t mlen;
+    int rc = begin_ranged_call(ctx, msg, len, lo, hi, t0, &m, &mlen);
+    if (rc) return rc;
+    CollectTally tally;
+    uint64_t sum = 0;
+    rc = collect_core(ctx, m, mlen, lo, hi, target, cap, &tally, recs, &sum);
+    if (rc) return rc;
+    hm_collect_stats st{};
+    st.kernel_ms = tally.kernel_ms;
+    st.total = sum;
+    st.ndev = (int)ctx->devs.size();
+    st.overflow = sum > cap ? 1 : 0;
+    st.nonces = tally.nonces;
+    st.launches = tally.launches;
     st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
                      .count();
     ctx->last_collect = st;

@@ -106,6 +106,8 @@ void device_free(Device& dv) {
     if (dv.find_many_ctl) (void)hipFree(dv.find_many_ctl);
     if (dv.collect_ctl) (void)hipFree(dv.collect_ctl);
     if (dv.collect_buf) (void)hipFree(dv.collect_buf);
+    if (dv.collect_many_ctl) (void)hipFree(dv.collect_many_ctl);
+    if (dv.collect_tags) (void)hipFree(dv.collect_tags);
     if (dv.verify_ctl) (void)hipFree(dv.verify_ctl);
     if (dv.verify_in) (void)hipFree(dv.verify_in);
     if (dv.verify_idx) (void)hipFree(dv.verify_idx);

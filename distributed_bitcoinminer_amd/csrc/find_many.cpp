@@ -44,18 +44,6 @@ struct Req {
     hipEvent_t a = nullptr, b = nullptr;
 };
 
-// A failure other than a timeout leaves nothing queued: every stream a
-// device has made is waited for (drain_failed: stream 0 and the events).
-int drain_streams(hm_ctx* ctx, int rc) {
-    if (rc == HM_ERR_TIMEOUT || ctx->abandoned) return rc;
-    for (Device& dv : ctx->devs) {
-        if (hipSetDevice(dv.ordinal) != hipSuccess) break;
-        for (int s = 1; s < dv.nmade; ++s)
-            if (host_wait(ctx, dv.stream[s]) != HM_OK) return rc;
-    }
-    return drain_failed(ctx, rc);
-}
-
 int find_chunk(hm_ctx* ctx, const hm_find_request* reqs, int n, int index0, hm_result* outs,
                int* found, hm_find_many_stats* st) {
     static const uint8_t empty_msg = 0;
@@ -193,6 +181,18 @@ int find_chunk(hm_ctx* ctx, const hm_find_request* reqs, int n, int index0, hm_r
 }
 
 }  // namespace
+
+// A failure other than a timeout leaves nothing queued: every stream a
+// device has made is waited for (drain_failed: stream 0 and the events).
+int drain_streams(hm_ctx* ctx, int rc) {
+    if (rc == HM_ERR_TIMEOUT || ctx->abandoned) return rc;
+    for (Device& dv : ctx->devs) {
+        if (hipSetDevice(dv.ordinal) != hipSuccess) break;
+        for (int s = 1; s < dv.nmade; ++s)
+            if (host_wait(ctx, dv.stream[s]) != HM_OK) return rc;
+    }
+    return drain_failed(ctx, rc);
+}
 
 // hm_find_many with ctx->mu held.
 int find_many_locked(hm_ctx* ctx, const hm_find_request* reqs, int n, hm_result* outs, int* found) {

@@ -8,6 +8,7 @@
 //   find.cpp      hm_find
 //   find_many.cpp hm_find_many
 //   collect.cpp   hm_collect
+//   collect_many.cpp hm_collect_many
 //   verify.cpp    hm_hash_many, hm_verify
 //   verify_many.cpp hm_verify_many
 //   api.cpp       the extern "C" entry points and the debug exports
@@ -120,6 +121,13 @@ struct Device {
     uint64_t* collect_ctl = nullptr;
     uint64_t* collect_buf = nullptr;
     size_t collect_cap = 0;
+    // hm_collect_many, made on first use: [0] the chunk's slot cursor, [1 + r] request r's total
+    // (kMaxBatch + 1 words); the tag buffer of collect_tags_cap words (the request of each record
+    // slot), grown like collect_buf.  The records go through collect_buf, which hm_collect and
+    // this call never use at once
+    uint64_t* collect_many_ctl = nullptr;
+    uint32_t* collect_tags = nullptr;
+    size_t collect_tags_cap = 0;
     // hm_hash_many / hm_verify, all made on first use: [0] total, [1] slot cursor (kernels.hpp
     // VerifyArgs); the chunk buffer of verify_in_bytes bytes (nonces, or 16-byte records) and the
     // index buffer of verify_idx_cap indices, grown like collect_buf
@@ -184,6 +192,7 @@ struct hm_ctx {
     uint32_t verify_chunk = 0;  // HM_OPT_VERIFY_CHUNK (test hook; 0 = kVerifyChunk)
     uint32_t verify_jobs = 0;   // HM_OPT_VERIFY_JOBS (test hook; 0 = kVerifyJobsMax)
     uint64_t find_window = 0;   // HM_OPT_FIND_WINDOW (test hook; 0 = kFusedNonces)
+    uint64_t collect_window = 0;  // HM_OPT_COLLECT_WINDOW (test hook; 0 = kFusedNonces)
     // host waits on GPU work while the call is still enqueuing (hm_stats.mid_call_syncs)
     bool enqueuing = false;
     int32_t mid_syncs = 0;
@@ -213,6 +222,8 @@ struct hm_ctx {
     hm_find_many_stats last_find_many{};
     bool have_verify_many_stats = false;  // and hm_verify_many
     hm_verify_many_stats last_verify_many{};
+    bool have_collect_many_stats = false;  // and hm_collect_many
+    hm_collect_many_stats last_collect_many{};
 };
 
 namespace hm {
@@ -407,8 +418,11 @@ int begin_ranged_call(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, 
 // a scan.  Returns rc.
 int drain_failed(hm_ctx* ctx, int rc);
 
-// ---- scan.cpp: the fused launch, shared with find_many.cpp ----
+// ---- scan.cpp: the fused launch, shared with find_many.cpp and collect_many.cpp ----
 bool fusible(const std::vector<SegPlan>& segs);
+// The task order of a fused launch without an early exit: costliest layout
+// first, larger segments first (the launch ends on its cheapest tasks).
+void fused_order(std::vector<SegPlan>* segs);
 // A fused launch as plan_fused lays it out.  The caller sets the outputs
 // (pa.result, pa.acc, pa.n_acc; fa.cand, fa.sums) and launches.
 struct FusedLaunch {
@@ -435,6 +449,28 @@ struct FindTally {
 int find_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_t hi, uint64_t target,
               FindTally* tally, hm_result* res, int* hit);
 
+// ---- find_many.cpp: shared with collect_many.cpp ----
+// A batch call that fails with rc leaves nothing queued: unless rc is a
+// timeout, every stream the devices have made is waited for, then
+// drain_failed (stream 0 and the events).  Returns rc.
+int drain_streams(hm_ctx* ctx, int rc);
+
+// ---- collect.cpp: hm_collect without its opening and its stats, for hm_collect_many's fallback ----
+struct CollectTally {
+    uint64_t nonces = 0;
+    int launches = 0;
+    double kernel_ms = 0;
+};
+// Every nonce of [lo, hi] whose hash is below target, on stream 0 through the
+// per-segment collect kernels: *recs and *total as collect_locked returns
+// them, the work added to *tally.  The call's deadline is already set.
+int collect_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_t hi,
+                 uint64_t target, size_t cap, CollectTally* tally, std::vector<hm_result>* recs,
+                 uint64_t* total);
+// Make dv's record buffer hold `cap` records (grown by at least doubling, the
+// old one retired).
+int collect_buffer(Device& dv, size_t cap);
+
 // ---- scan.cpp, find.cpp, collect.cpp, verify.cpp: the entry points' bodies, ctx->mu held ----
 int scan_many_locked(hm_ctx* ctx, const hm_request* reqs, int n, hm_result* outs);
 int find_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
@@ -443,6 +479,12 @@ int find_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64
 int find_many_locked(hm_ctx* ctx, const hm_find_request* reqs, int n, hm_result* outs, int* found);
 int collect_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
                    uint64_t target, size_t cap, std::vector<hm_result>* recs, uint64_t* total);
+// hm_collect_many: (*totals)[i] for i < n, *total their sum, and *recs (every
+// record, request-major, ascending by nonce inside a request) when *total <=
+// cap; empty otherwise.
+int collect_many_locked(hm_ctx* ctx, const hm_collect_request* reqs, int n, size_t cap,
+                        std::vector<uint64_t>* totals, std::vector<hm_result>* recs,
+                        uint64_t* total);
 // hm_hash_many (recs null: `list` holds n nonces, *out gets the n hashes) and
 // hm_verify (recs: n records; *out gets the bad indices, ascending, when
 // *bad <= cap and stays empty otherwise).

@@ -1,8 +1,9 @@
 // host_scan.cpp -- hm_scan_cpu, hm_find_cpu, hm_find_many_cpu, hm_collect_cpu,
-// hm_hash_many_cpu, hm_verify_cpu and hm_verify_many_cpu: the min-hash scan, the
-// first-below-target search (ABI 1.10) and its batch form (ABI 1.13), the
-// all-below-target collection (ABI 1.11), the recheck of a list (ABI 1.12) and
-// of the lists of many messages (ABI 1.14), on the host's cores.
+// hm_collect_many_cpu, hm_hash_many_cpu, hm_verify_cpu and hm_verify_many_cpu:
+// the min-hash scan, the first-below-target search (ABI 1.10) and its batch
+// form (ABI 1.13), the all-below-target collection (ABI 1.11) and its batch
+// form (ABI 1.15), the recheck of a list (ABI 1.12) and of the lists of many
+// messages (ABI 1.14), on the host's cores.
 //
 // SURVEY §8(b)'s liveness path.  The reference miner always answers a
 // Request with a Result (cmu440/bitcoin/miner/miner.go:60-62); a GPU miner
@@ -552,6 +553,42 @@ extern "C" int hm_collect_cpu(const uint8_t* msg, size_t len, uint64_t lo, uint6
                 at += p.recs.size();
             }
         }
+        *total = sum;
+        return HM_OK;
+    } catch (const std::bad_alloc&) {
+        return HM_ERR_NOMEM;
+    } catch (...) {
+        return HM_ERR_INTERNAL;
+    }
+}
+
+extern "C" int hm_collect_many_cpu(const hm_collect_request* reqs, int n, int threads,
+                                   uint64_t* totals, hm_result* out, size_t cap,
+                                   uint64_t* total) {
+    if (n < 0 || (n > 0 && (!reqs || !totals)) || !total || cap > HM_COLLECT_CAP_MAX ||
+        (cap && !out))
+        return HM_ERR_INVALID;
+    for (int r = 0; r < n; ++r)
+        if (!reqs[r].msg && reqs[r].len) return HM_ERR_INVALID;
+    try {
+        // request-major: request r's records go behind those of the requests
+        // before it, into what is left of `cap`; once one does not fit the call
+        // has overflowed and the rest are counts
+        std::vector<uint64_t> per((size_t)n, 0);
+        std::vector<hm_result> all(cap);
+        uint64_t sum = 0;
+        for (int r = 0; r < n; ++r) {
+            const hm_collect_request& q = reqs[r];
+            const size_t room = sum <= cap ? cap - (size_t)sum : 0;
+            const int rc = hm_collect_cpu(q.msg, q.msg ? q.len : 0, q.lo, q.hi, q.target, threads,
+                                          room ? all.data() + sum : nullptr, room, &per[r]);
+            if (rc) return rc;
+            if (sum + per[r] < sum) return HM_ERR_INTERNAL;
+            sum += per[r];
+        }
+        // all outputs from here on, none before
+        for (int r = 0; r < n; ++r) totals[r] = per[r];
+        if (sum <= cap && sum) memcpy(out, all.data(), (size_t)sum * sizeof(hm_result));
         *total = sum;
         return HM_OK;
     } catch (const std::bad_alloc&) {

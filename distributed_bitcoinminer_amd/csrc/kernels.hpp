@@ -274,6 +274,19 @@ struct CollectGenericArgs {
     GenericArgs g;
     CollectArgs k;
 };
+// hm_collect_many (fused_collect_kernels.hip): one request,
+// every segment in one launch.  `k.total` is the REQUEST's total word, zeroed
+// by the planner launch (FusedPlanArgs::acc, n_acc = 1); `k.cursor` and
+// `k.out` are the device's one cursor and record buffer, shared by the
+// requests of a chunk, so each record's slot also gets the request's index in
+// `tags` (cap words; null when cap == 0).  a.cand, a.sums, a.flags and a.trace
+// are unused.
+struct FusedCollectArgs {
+    FusedArgs a;
+    CollectArgs k;
+    uint32_t* tags;
+    uint32_t request;
+};
 
 // ---------------------------------------------------------------------------
 // hm_hash_many / hm_verify (verify_kernels.hip, DESIGN.md "Recheck a list"):

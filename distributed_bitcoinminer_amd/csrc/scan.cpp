@@ -226,6 +226,17 @@ int fused_rank(const SegPlan& g) {
     return g.trailer ? 2 : 3;                  // 640 nonces, 2 or 1 compressions
 }
 
+}  // namespace
+
+void fused_order(std::vector<SegPlan>* segs) {
+    std::stable_sort(segs->begin(), segs->end(), [](const SegPlan& a, const SegPlan& b) {
+        if (fused_rank(a) != fused_rank(b)) return fused_rank(a) < fused_rank(b);
+        return a.hi - a.lo > b.hi - b.lo;
+    });
+}
+
+namespace {
+
 // Enqueue every segment of one request as ONE fused launch on stream si:
 // hm_fused_plan_kernel (records, tables, counter; and, when `seed_best`, the
 // (MaxUint64, 0) seed of *best and zeroed coverage sums) -> hm_fused_kernel
@@ -234,10 +245,7 @@ int fused_rank(const SegPlan& g) {
 int enqueue_fused(hm_ctx* ctx, Device& dv, const MsgPlan& mp, std::vector<SegPlan> segs, int si,
                   uint64_t* best, bool seed_best) {
     hipStream_t st = dv.stream[si];
-    std::stable_sort(segs.begin(), segs.end(), [](const SegPlan& a, const SegPlan& b) {
-        if (fused_rank(a) != fused_rank(b)) return fused_rank(a) < fused_rank(b);
-        return a.hi - a.lo > b.hi - b.lo;
-    });
+    fused_order(&segs);
     FusedLaunch fl;
     int rc = plan_fused(ctx, dv, mp, segs, si, ctx->fused_flags, &fl);
     if (rc) return rc;

@@ -20,6 +20,10 @@ KernelName kernel_name(Family family, int kind, const SegPlan* s) {
         fn = "hm_fused_find_kernel";
         arg = "FusedFindArgs";
     }
+    if (family == Family::Collect && kind == HM_KIND_FUSED) {  // fused_collect_kernels.hip
+        fn = "hm_fused_collect_kernel";
+        arg = "FusedCollectArgs";
+    }
     char targs[48] = "", shown[48] = "";
     if (kind == HM_KIND_TILED) {  // hm_*tiled*_kernel<W1, STRADDLE, TRAILER>
         snprintf(targs, sizeof targs, "ILi%dELb%dELb%dEEEv", s->W1, s->straddle ? 1 : 0,

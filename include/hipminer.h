@@ -657,6 +657,101 @@ typedef struct hm_verify_many_stats {
  * hm_verify_many's stats; HM_ERR_INVALID before the first one. */
 int hm_verify_many_stats_sized(const hm_ctx *ctx, hm_verify_many_stats *out, size_t size);
 
+/* ABI 1.15: a batch of collects.  hm_collect makes one launch per digit
+ * segment piece, on stream 0, one blocking call per message; a pool that hands
+ * out small work units wants, per job, the shares below the share target (or,
+ * with no buffer, the hit count a difficulty is set from) for many messages at
+ * once.
+ *
+ *   totals[i] = the *total that hm_collect(reqs[i]) returns, always exact.
+ *   *total    = the sum of the per-request totals.
+ * Strict '<' as in hm_collect; target = 0 and lo > hi count 0; hi may be
+ * UINT64_MAX, and nonce UINT64_MAX is an ordinary record.
+ *
+ * The size-query idiom, with ONE cap for the whole call (as hm_verify_many):
+ *   *total <= cap: out[0 .. *total) holds every record, request-major:
+ *                  request i's records start at totals[0] + ... + totals[i-1],
+ *                  and inside a request they ascend by nonce, bit for bit what
+ *                  hm_collect writes for that request.  Nothing at or beyond
+ *                  out[*total] is touched.
+ *   *total >  cap: out is not written at all.  totals and *total still are.
+ *   cap == 0 with out == NULL gives the pure counts.
+ *
+ * Requests may repeat; each is answered on its own.  n == 0 is HM_OK with
+ * *total = 0 and enqueues nothing.  HM_ERR_INVALID: n < 0; n > 0 with reqs or
+ * totals NULL; total == NULL; cap > HM_COLLECT_CAP_MAX; cap > 0 with
+ * out == NULL; any request with msg == NULL and len > 0 (msg == NULL with
+ * len == 0 is the empty message).  Outputs are written only on HM_OK, all of
+ * them or none.  An abandoned context returns HM_ERR_TIMEOUT.
+ * HM_OPT_DEADLINE_MS applies to the whole call (auto: 2 s + 8 x the sum of what
+ * hm_collect's auto rule models for each request).
+ *
+ * A request of at most 2^27 nonces whose digit segments all fit a fused launch
+ * (all, but for chained layouts of more than four final-block digits) runs as
+ * ONE launch of the fused collect kernel: request r whole on
+ * device r mod ndev, round-robin over that device's streams (HM_OPT_STREAMS, as
+ * hm_find_many), every request of a chunk of 64 enqueued on every device before
+ * the host waits on any.  Each request has its own total word; the records of
+ * a chunk's requests share the device's buffer and carry a request tag, and
+ * the host groups them by tag and sorts each group by nonce.  Any other
+ * request takes hm_collect's per-segment path WHOLE, one request after another
+ * (there is no fused prefix: without an early exit it buys nothing).
+ * HM_OPT_FORCE_GENERIC and HM_OPT_GRID_PER_CU are honoured as the fused scan
+ * launch honours them; HM_OPT_FUSED = 0 sends every request down the
+ * per-segment path (the in-library A/B); the RCCL option does not apply.  The
+ * host recomputes nothing: a record carries the hash the kernel formed.  Each
+ * device keeps hm_collect's record buffer (the two calls share it), a buffer
+ * of `cap` 32-bit tags and 65 control words, made on first use, grown when a
+ * larger cap arrives and kept until hm_close.  The call changes nothing that
+ * any other *_stats* export reports.
+ *
+ * Measured per request against a loop of hm_collect (DESIGN.md §3f has the
+ * rows): 64 requests over [0, 10^7] take 0.59 (an 8-byte message) and 0.36 (a
+ * 120-byte one) of the loop's time, 64 requests over [0, 10^5] a third, a LONE
+ * request over [0, 10^7] 0.85 and 0.78 (one launch that plans its whole range
+ * first, against eight).  No measured row loses; a request of more than 2^27
+ * nonces is hm_collect's own path at hm_collect's own time. */
+typedef struct hm_collect_request {
+    const uint8_t *msg;   /* borrowed for the call; may be NULL when len == 0 */
+    size_t len;
+    uint64_t lo, hi;      /* inclusive */
+    uint64_t target;
+} hm_collect_request;     /* 40 bytes, the shape of hm_find_request */
+
+int hm_collect_many(hm_ctx *ctx, const hm_collect_request *reqs, int n, uint64_t *totals,
+                    hm_result *out, size_t cap, uint64_t *total);
+
+/* The same answers on the host's cores, no GPU: hm_collect_cpu request by
+ * request (`threads` as there), under the same contract, the all-or-nothing
+ * `out` included. */
+int hm_collect_many_cpu(const hm_collect_request *reqs, int n, int threads, uint64_t *totals,
+                        hm_result *out, size_t cap, uint64_t *total);
+
+/* Work accounting of the most recent successful hm_collect_many on a context.
+ * The struct only grows at its end. */
+typedef struct hm_collect_many_stats {
+    double wall_ms;    /* host wall time of the call                             */
+    double kernel_ms;  /* summed HIP-event time of the fused collect launches and
+                          of any fallback launches                               */
+    uint64_t nonces;   /* nonces covered                                         */
+    uint64_t total;    /* the call's *total                                      */
+    uint64_t tasks;    /* task ids of the fused launches                         */
+    int32_t requests;  /* n                                                      */
+    int32_t fused;     /* requests answered by their fused launch alone          */
+    int32_t fallback;  /* requests that took the per-segment path.  A request
+                          that enqueues nothing (lo > hi, target = 0) counts in
+                          neither                                                */
+    int32_t launches;  /* fused collect launches plus fallback launches          */
+    int32_t ndev;      /* devices of the context                                 */
+    int32_t overflow;  /* 1: *total > cap, `out` was not written; else 0         */
+} hm_collect_many_stats;
+#define HM_COLLECT_MANY_STATS_SIZE_1_15 64 /* ABI 1.15 */
+
+/* Writes at most `size` bytes (pass sizeof the struct as the caller compiled
+ * it; >= HM_COLLECT_MANY_STATS_SIZE_1_15) of the last successful
+ * hm_collect_many's stats; HM_ERR_INVALID before the first one. */
+int hm_collect_many_stats_sized(const hm_ctx *ctx, hm_collect_many_stats *out, size_t size);
+
 int hm_set_option(hm_ctx *ctx, int opt, int64_t value);
 
 const char *hm_strerror(int rc);

@@ -64,6 +64,11 @@ extern "C" {
                                   so a batch of a few requests crosses launch
                                   boundaries; with HM_OPT_VERIFY_CHUNK, which
                                   that call honours as its records bound       */
+#define HM_OPT_COLLECT_WINDOW 22 /* test hook (64..2^27; 0 = default 2^27; ABI
+                                  1.15): a request of more nonces than this is
+                                  not fused by hm_collect_many, so a test can
+                                  put the fused/unfused boundary at a few
+                                  hundred nonces                               */
 
 /* The embedded scan code object: *p = its first byte, returns its size.
  * bench.py hashes these bytes to match a PMC summary to the build that runs. */
