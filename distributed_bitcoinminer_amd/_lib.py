@@ -43,6 +43,7 @@ HM_OPT_VERIFY_CHUNK = 19
 HM_OPT_FIND_WINDOW = 20
 HM_OPT_VERIFY_JOBS = 21
 HM_OPT_COLLECT_WINDOW = 22
+HM_OPT_FIND_K_BUF = 23
 HM_MERGE_NONE, HM_MERGE_HOST, HM_MERGE_RCCL = 0, 1, 2
 
 
@@ -106,6 +107,18 @@ class hm_find_many_stats(ctypes.Structure):
                 ("found", ctypes.c_int32), ("fused", ctypes.c_int32),
                 ("fallback", ctypes.c_int32), ("launches", ctypes.c_int32),
                 ("ndev", ctypes.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class hm_find_k_stats(ctypes.Structure):
+    """hm_find_k_stats of include/hipminer.h (ABI 1.16)."""
+    _fields_ = [("wall_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
+                ("nonces_enqueued", ctypes.c_uint64), ("tasks_total", ctypes.c_uint64),
+                ("tasks_run", ctypes.c_uint64), ("records", ctypes.c_uint64),
+                ("launches", ctypes.c_int32), ("ndev", ctypes.c_int32),
+                ("found", ctypes.c_int32), ("fallback", ctypes.c_int32)]
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -180,6 +193,7 @@ class hm_collect_many_stats(ctypes.Structure):
 
 
 HM_COLLECT_CAP_MAX = 1 << 24
+HM_FIND_K_MAX = 1 << 20
 HM_VERIFY_CAP_MAX = 1 << 20
 
 _lib = None
@@ -263,6 +277,17 @@ def load() -> ctypes.CDLL:
         lib.hm_find_many_stats_sized.argtypes = [ctypes.c_void_p,
                                                  ctypes.POINTER(hm_find_many_stats),
                                                  ctypes.c_size_t]
+        lib.hm_find_k.restype = ctypes.c_int
+        lib.hm_find_k.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint64,
+                                  ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t,
+                                  ctypes.POINTER(hm_result), ctypes.POINTER(ctypes.c_size_t)]
+        lib.hm_find_k_cpu.restype = ctypes.c_int
+        lib.hm_find_k_cpu.argtypes = [u8p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64,
+                                      ctypes.c_uint64, ctypes.c_size_t, ctypes.c_int,
+                                      ctypes.POINTER(hm_result), ctypes.POINTER(ctypes.c_size_t)]
+        lib.hm_find_k_stats_sized.restype = ctypes.c_int
+        lib.hm_find_k_stats_sized.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_find_k_stats),
+                                              ctypes.c_size_t]
         lib.hm_collect.restype = ctypes.c_int
         lib.hm_collect.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint64,
                                    ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(hm_result),
@@ -435,6 +460,22 @@ class Context:
             raise HipMinerError(rc, "hm_find_many_stats_sized")
         return st.as_dict()
 
+    def find_k(self, msg, lo: int, hi: int, target: int, k: int):
+        """hm_find_k (ABI 1.16): the (hash, nonce) of the k LOWEST nonces in the
+        inclusive [lo, hi] whose hash is below `target`, ascending by nonce --
+        fewer than k when the range holds fewer; the call stops early once the
+        k-th is known."""
+        return _find_k(lambda m, out, n: self._lib.hm_find_k(
+            self._h, m, len(m), lo, hi, target, k, out, n), "hm_find_k", msg, k)
+
+    def find_k_stats(self) -> dict:
+        """hm_find_k_stats_sized: work accounting of the last find_k on this context."""
+        st = hm_find_k_stats()
+        rc = self._lib.hm_find_k_stats_sized(self._h, ctypes.byref(st), ctypes.sizeof(st))
+        if rc != HM_OK:
+            raise HipMinerError(rc, "hm_find_k_stats_sized")
+        return st.as_dict()
+
     def collect(self, msg, lo: int, hi: int, target: int, cap: int):
         """hm_collect (ABI 1.11): (total, records).  total = the number of
         nonces in the inclusive [lo, hi] whose hash is below `target`, always
@@ -598,6 +639,28 @@ def find_many_cpu(requests, threads: int = 0):
     """hm_find_many_cpu (ABI 1.13): Context.find_many's answers on the host's cores."""
     return _find_many(lambda arr, n, outs, found: load().hm_find_many_cpu(
         arr, n, threads, outs, found), "hm_find_many_cpu", requests)
+
+
+def _find_k(call, what: str, msg, k: int):
+    """Run a find_k entry point with a buffer of k records and shape its
+    answer: a list of (hash, nonce)."""
+    m = as_bytes(msg)
+    buf = (hm_result * k)() if 0 < k <= HM_FIND_K_MAX else None
+    n = ctypes.c_size_t(0)
+    rc = call(m, buf, ctypes.byref(n))
+    if rc != HM_OK:
+        raise HipMinerError(rc, what)
+    t = int(n.value)
+    if t == 0:
+        return []
+    words = struct.unpack_from(f"={2 * t}Q", buf)
+    return list(zip(words[0::2], words[1::2]))
+
+
+def find_k_cpu(msg, lo: int, hi: int, target: int, k: int, threads: int = 0):
+    """hm_find_k_cpu (ABI 1.16): Context.find_k's answer on the host's cores."""
+    return _find_k(lambda m, out, n: load().hm_find_k_cpu(
+        m, len(m), lo, hi, target, k, threads, out, n), "hm_find_k_cpu", msg, k)
 
 
 def _collect(call, what: str, msg, cap: int):

@@ -26,6 +26,8 @@
 //   through the job kernel of verify_many_kernels.hip.
 //   hm_collect_many (ABI 1.15): collect_many.cpp, one fused launch of
 //   fused_collect_kernels.hip per request, hm_collect's path for the rest.
+//   hm_find_k (ABI 1.16): find_k.cpp over hm_find's walk, the kernels of
+//   find_k_kernels.hip, hm_collect's path when its record buffer overflows.
 //   The scan kernels come from their own code object (scan_kernels.hip ->
 //   align_loops.py -> hipminer_scan.hsaco, embedded by scan_blob.S), loaded
 //   per device with hipModuleLoadData and launched with hipModuleLaunchKernel.
@@ -61,7 +63,8 @@ uint64_t hm_hash(const uint8_t* msg, size_t len, uint64_t nonce) {
 // 1.13: hm_find_many, hm_find_many_cpu, hm_find_many_stats_sized, HM_OPT_FIND_WINDOW
 // 1.14: hm_verify_many, hm_verify_many_cpu, hm_verify_many_stats_sized, HM_OPT_VERIFY_JOBS
 // 1.15: hm_collect_many, hm_collect_many_cpu, hm_collect_many_stats_sized, HM_OPT_COLLECT_WINDOW
-int hm_version(void) { return (1 << 16) | 15; }
+// 1.16: hm_find_k, hm_find_k_cpu, hm_find_k_stats_sized, HM_OPT_FIND_K_BUF
+int hm_version(void) { return (1 << 16) | 16; }
 
 // The digest of the sources this library was built from (build_id.py), kept
 // in the binary behind a tag so tools can read it without loading the library.
@@ -189,6 +192,11 @@ int hm_set_option(hm_ctx* ctx, int opt, int64_t value) {
             if (value != 0 && (value < 64 || value > (int64_t)kFusedNonces)) return HM_ERR_INVALID;
             ctx->collect_window = (uint64_t)value;
             return HM_OK;
+        case HM_OPT_FIND_K_BUF:
+            if (value != 0 && (value < 1 || value > (int64_t)HM_COLLECT_CAP_MAX))
+                return HM_ERR_INVALID;
+            ctx->find_k_buf = (uint32_t)value;
+            return HM_OK;
         case HM_OPT_GRID_PER_CU:
             if (value < 0 || value > 32) return HM_ERR_INVALID;
             ctx->grid_per_cu = (int)value;
@@ -284,6 +292,27 @@ int hm_find_many_stats_sized(const hm_ctx* ctx, hm_find_many_stats* out, size_t 
     std::lock_guard<std::mutex> g(ctx->mu);
     if (!ctx->have_find_many_stats) return HM_ERR_INVALID;
     memcpy(out, &ctx->last_find_many, std::min(size, sizeof(hm_find_many_stats)));
+    return HM_OK;
+}
+
+int hm_find_k(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
+              uint64_t target, size_t k, hm_result* out, size_t* n) {
+    if (!ctx || !out || !n || (!msg && len) || k == 0 || k > HM_FIND_K_MAX) return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    std::vector<hm_result> recs;
+    int rc = guarded([&] { return find_k_locked(ctx, msg, len, lo, hi, target, k, &recs); });
+    if (rc) return rc;
+    // nothing at or beyond out[*n] is touched
+    if (!recs.empty()) memcpy(out, recs.data(), recs.size() * sizeof(hm_result));
+    *n = recs.size();
+    return HM_OK;
+}
+
+int hm_find_k_stats_sized(const hm_ctx* ctx, hm_find_k_stats* out, size_t size) {
+    if (!ctx || !out || size < HM_FIND_K_STATS_SIZE_1_16) return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!ctx->have_find_k_stats) return HM_ERR_INVALID;
+    memcpy(out, &ctx->last_find_k, std::min(size, sizeof(hm_find_k_stats)));
     return HM_OK;
 }
 

@@ -29,37 +29,23 @@
 //
 // A hit at nonce MaxUint64 cannot be told from "none" in the stop word, so
 // the kernels never publish it and the host tests that one nonce itself.
+//
+// The walk itself -- FindDev, find_next_step, find_issue (hm_internal.hpp) and
+// find_collect -- is shared with hm_find_k (find_k.cpp), which runs it over
+// its own kernels, trailer and control words.
 // ---------------------------------------------------------------------------
 #include "hm_internal.hpp"
 
 namespace hm {
-namespace {
-
-constexpr int kFindLookahead = 4;
-
-// One device's walk through its shard of a piece.
-struct FindDev {
-    std::vector<SegPlan> segs;  // the shard's segments (one digit count: one)
-    size_t si = 0;
-    bool seg_open = false;      // `walk` is on segs[si]
-    SegWalk walk;
-    int inflight = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
-    uint64_t word = ~0ull, run = 0;  // last readback
-};
-
-// Issue the device's next launch whose smallest nonce is <= best (the lowest
-// hit known; MaxUint64 = none), between two timing events, and count it.
-// *issued = false: nothing left to issue in this piece.  A pruned launch
-// enqueues nothing.
-int find_issue(hm_ctx* ctx, Device& dv, FindDev& fd, const MsgPlan& mp, uint64_t target,
-               uint64_t best, FindTally& tally, bool* issued) {
-    *issued = false;
+// The device's next launch at or below `best`, planned but not launched.
+int find_next_step(hm_ctx* ctx, Device& dv, FindDev& fd, const MsgPlan& mp, Family family,
+                   uint64_t best, SegStep* step, bool* have) {
+    *have = false;
     for (;;) {
         if (fd.si >= fd.segs.size()) return HM_OK;
         const SegPlan& s = fd.segs[fd.si];
         if (!fd.seg_open) {
-            int rc = fd.walk.open(ctx, dv, mp, 0, s, Family::Find, kFindGenericNonces);
+            int rc = fd.walk.open(ctx, dv, mp, 0, s, family, kFindGenericNonces);
             if (rc) return rc;
             fd.seg_open = true;
         }
@@ -76,41 +62,20 @@ int find_issue(hm_ctx* ctx, Device& dv, FindDev& fd, const MsgPlan& mp, uint64_t
             else fd.walk.skip_epoch();
             continue;
         }
-        SegStep step;
-        fd.walk.next(&step);
-        FindArgs fa;
-        fa.word = dv.find_ctl;
-        fa.tasks_run = dv.find_ctl + 1;
-        fa.target = target;
-        fa.launch_lo = step.base;
-        hipEvent_t a, b;
-        int rc = next_event(dv, &a);
-        if (rc) return rc;
-        rc = next_event(dv, &b);
-        if (rc) return rc;
-        fd.evs.push_back({a, b});
-        rc = fd.walk.launch(step, fa, a, b);
-        if (rc) return rc;
-        tally.nonces += step.nonces;
-        tally.tasks += step.ntasks;
-        ++tally.launches;
-        ++fd.inflight;
-        *issued = true;
+        fd.walk.next(step);
+        *have = true;
         return HM_OK;
     }
 }
 
-// Wait for the device's launches in flight and read its stop word and task
-// counter back.
-int find_collect(hm_ctx* ctx, Device& dv, FindDev& fd, FindTally& tally) {
+// Wait for the device's launches in flight and read its control words back.
+int find_collect(hm_ctx* ctx, Device& dv, FindDev& fd, FindTally& tally, const uint64_t* dev_ctl,
+                 int nwords) {
     HIPCHK(hipSetDevice(dv.ordinal));
     int rc = host_wait(ctx, dv.stream[0]);
     if (rc) return rc;
-    uint64_t ctl[2];
-    rc = host_read(ctx, ctl, dv.find_ctl, sizeof ctl);
+    rc = host_read(ctx, fd.ctl, dev_ctl, (size_t)nwords * sizeof(uint64_t));
     if (rc) return rc;
-    fd.word = ctl[0];
-    fd.run = ctl[1];
     for (const auto& ev : fd.evs) {
         float ms = 0.f;
         HIPCHK(hipEventElapsedTime(&ms, ev.first, ev.second));
@@ -121,8 +86,6 @@ int find_collect(hm_ctx* ctx, Device& dv, FindDev& fd, FindTally& tally) {
     fd.inflight = 0;
     return HM_OK;
 }
-
-}  // namespace
 
 int find_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_t hi, uint64_t target,
               FindTally* tally_out, hm_result* out, int* found) {
@@ -158,7 +121,15 @@ int find_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_t 
                     HIPCHK(hipSetDevice(dv.ordinal));
                     while (fds[i].inflight < kFindLookahead) {
                         bool issued = false;
-                        rc = find_issue(ctx, dv, fds[i], mp, target, best, tally, &issued);
+                        rc = find_issue(ctx, dv, fds[i], mp, Family::Find, best, tally, &issued,
+                                        [&](uint64_t launch_lo) {
+                                            FindArgs fa;
+                                            fa.word = dv.find_ctl;
+                                            fa.tasks_run = dv.find_ctl + 1;
+                                            fa.target = target;
+                                            fa.launch_lo = launch_lo;
+                                            return fa;
+                                        });
                         if (rc) return drain_failed(ctx, rc);
                         if (!issued) break;
                     }
@@ -167,13 +138,13 @@ int find_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_t 
                 if (!any) break;
                 for (int i = 0; i < ndev; ++i) {
                     if (!fds[i].inflight) continue;
-                    rc = find_collect(ctx, ctx->devs[i], fds[i], tally);
+                    rc = find_collect(ctx, ctx->devs[i], fds[i], tally, ctx->devs[i].find_ctl, 2);
                     if (rc) return drain_failed(ctx, rc);
-                    best = std::min(best, fds[i].word);
+                    best = std::min(best, fds[i].ctl[0]);
                 }
             }
         }
-        for (const FindDev& fd : fds) tally.run += fd.run;
+        for (const FindDev& fd : fds) tally.run += fd.ctl[1];
     }
     hm_result res{~0ull, 0};
     int hit = 0;

@@ -7,6 +7,7 @@
 //   scan.cpp      hm_scan_many: batching, the fused launch, merge, stats
 //   find.cpp      hm_find
 //   find_many.cpp hm_find_many
+//   find_k.cpp    hm_find_k
 //   collect.cpp   hm_collect
 //   collect_many.cpp hm_collect_many
 //   verify.cpp    hm_hash_many, hm_verify
@@ -116,6 +117,9 @@ struct Device {
     uint64_t* find_ctl = nullptr;  // hm_find: [0] the stop word, [1] tasks run (kernels.hpp FindArgs)
     // hm_find_many, made on first use: [kMaxBatch][2], request r's (stop word, tasks run)
     uint64_t* find_many_ctl = nullptr;
+    // hm_find_k, made on first use: the kFkWords control words (kernels.hpp FindKArgs).  The
+    // records go through collect_buf, which hm_collect and this call never use at once
+    uint64_t* find_k_ctl = nullptr;
     // hm_collect: [0] total, [1] slot cursor (kernels.hpp CollectArgs), and the record buffer of
     // collect_cap records, grown when a larger cap arrives (the old one joins `retired`)
     uint64_t* collect_ctl = nullptr;
@@ -193,6 +197,7 @@ struct hm_ctx {
     uint32_t verify_jobs = 0;   // HM_OPT_VERIFY_JOBS (test hook; 0 = kVerifyJobsMax)
     uint64_t find_window = 0;   // HM_OPT_FIND_WINDOW (test hook; 0 = kFusedNonces)
     uint64_t collect_window = 0;  // HM_OPT_COLLECT_WINDOW (test hook; 0 = kFusedNonces)
+    uint32_t find_k_buf = 0;      // HM_OPT_FIND_K_BUF (test hook; 0 = min(cap max, 2k + 4096))
     // host waits on GPU work while the call is still enqueuing (hm_stats.mid_call_syncs)
     bool enqueuing = false;
     int32_t mid_syncs = 0;
@@ -224,6 +229,8 @@ struct hm_ctx {
     hm_verify_many_stats last_verify_many{};
     bool have_collect_many_stats = false;  // and hm_collect_many
     hm_collect_many_stats last_collect_many{};
+    bool have_find_k_stats = false;  // and hm_find_k
+    hm_find_k_stats last_find_k{};
 };
 
 namespace hm {
@@ -248,9 +255,9 @@ void call_deadline(hm_ctx* ctx, const hm_request* reqs, int n,
 void list_deadline(hm_ctx* ctx, size_t n, std::chrono::steady_clock::time_point t0);
 
 // ---- seg_walk.cpp ----
-// Which kernels run a segment: the scan's, its checked variants, hm_find's or
-// hm_collect's.
-enum class Family { Scan, ScanCsum, Find, Collect };
+// Which kernels run a segment: the scan's, its checked variants, hm_find's,
+// hm_collect's or hm_find_k's.
+enum class Family { Scan, ScanCsum, Find, Collect, FindK };
 // The kernel of `family` for a segment of `kind` (s: the tiled instantiation's
 // template arguments; unused otherwise): its mangled name in
 // hipminer_scan.hsaco and the name rocprofv3 prints (sans arguments).
@@ -296,8 +303,8 @@ struct SegStep {
     uint32_t unit0;
 };
 // What follows a step's argument block in the kernel's parameter: nothing
-// (scan), FindArgs or CollectArgs -- the layout of kernels.hpp's Find*Args and
-// Collect*Args.
+// (scan), FindArgs, CollectArgs or FindKArgs -- the layout of kernels.hpp's
+// Find*Args, Collect*Args and FindK*Args.
 struct NoTrailer {};
 template <typename Base, typename Trailer>
 struct WithTrailer {
@@ -309,7 +316,10 @@ static_assert(sizeof(WithTrailer<TiledArgs, FindArgs>) == sizeof(FindTiledArgs) 
               sizeof(WithTrailer<GenericArgs, FindArgs>) == sizeof(FindGenericArgs) &&
               sizeof(WithTrailer<TiledArgs, CollectArgs>) == sizeof(CollectTiledArgs) &&
               sizeof(WithTrailer<ChainedArgs, CollectArgs>) == sizeof(CollectChainedArgs) &&
-              sizeof(WithTrailer<GenericArgs, CollectArgs>) == sizeof(CollectGenericArgs));
+              sizeof(WithTrailer<GenericArgs, CollectArgs>) == sizeof(CollectGenericArgs) &&
+              sizeof(WithTrailer<TiledArgs, FindKArgs>) == sizeof(FindKTiledArgs) &&
+              sizeof(WithTrailer<ChainedArgs, FindKArgs>) == sizeof(FindKChainedArgs) &&
+              sizeof(WithTrailer<GenericArgs, FindKArgs>) == sizeof(FindKGenericArgs));
 
 // A resumable cursor over the launches of one segment on one device and
 // stream.  Generic segments run in chunks of `generic_chunk` nonces; tiled ones
@@ -449,6 +459,53 @@ struct FindTally {
 int find_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_t hi, uint64_t target,
               FindTally* tally, hm_result* res, int* hit);
 
+// ---- find.cpp: the early-exit walk, shared with find_k.cpp ----
+constexpr int kFindLookahead = 4;  // launches in flight per device
+// One device's walk through its shard of a piece.
+struct FindDev {
+    std::vector<SegPlan> segs;  // the shard's segments (one digit count: one)
+    size_t si = 0;
+    bool seg_open = false;      // `walk` is on segs[si]
+    SegWalk walk;
+    int inflight = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
+    uint64_t ctl[kFkWords] = {~0ull};  // last readback of the call's control words ([0]: stop)
+};
+// Plan the device's next launch whose smallest nonce is <= best (the pruning
+// bound; MaxUint64 = none), opening segments with `family`'s kernels; a pruned
+// launch is dropped.  false in *have: nothing left to issue in this piece.
+int find_next_step(hm_ctx* ctx, Device& dv, FindDev& fd, const MsgPlan& mp, Family family,
+                   uint64_t best, SegStep* step, bool* have);
+// Issue that launch with the trailer make(step.base) between two timing events
+// and count it.  *issued = false: nothing left to issue in this piece.
+template <typename Make>
+int find_issue(hm_ctx* ctx, Device& dv, FindDev& fd, const MsgPlan& mp, Family family,
+               uint64_t best, FindTally& tally, bool* issued, Make&& make) {
+    *issued = false;
+    SegStep step;
+    bool have = false;
+    int rc = find_next_step(ctx, dv, fd, mp, family, best, &step, &have);
+    if (rc || !have) return rc;
+    hipEvent_t a, b;
+    rc = next_event(dv, &a);
+    if (rc) return rc;
+    rc = next_event(dv, &b);
+    if (rc) return rc;
+    fd.evs.push_back({a, b});
+    rc = fd.walk.launch(step, make(step.base), a, b);
+    if (rc) return rc;
+    tally.nonces += step.nonces;
+    tally.tasks += step.ntasks;
+    ++tally.launches;
+    ++fd.inflight;
+    *issued = true;
+    return HM_OK;
+}
+// Wait for the device's launches in flight and read the call's first `nwords`
+// control words at dev_ctl back into fd.ctl.
+int find_collect(hm_ctx* ctx, Device& dv, FindDev& fd, FindTally& tally, const uint64_t* dev_ctl,
+                 int nwords);
+
 // ---- find_many.cpp: shared with collect_many.cpp ----
 // A batch call that fails with rc leaves nothing queued: unless rc is a
 // timeout, every stream the devices have made is waited for, then
@@ -482,6 +539,9 @@ int collect_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uin
 // hm_collect_many: (*totals)[i] for i < n, *total their sum, and *recs (every
 // record, request-major, ascending by nonce inside a request) when *total <=
 // cap; empty otherwise.
+// hm_find_k: *recs = the min(k, hits) lowest records, ascending by nonce.
+int find_k_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
+                  uint64_t target, size_t k, std::vector<hm_result>* recs);
 int collect_many_locked(hm_ctx* ctx, const hm_collect_request* reqs, int n, size_t cap,
                         std::vector<uint64_t>* totals, std::vector<hm_result>* recs,
                         uint64_t* total);

@@ -1,9 +1,11 @@
 // host_scan.cpp -- hm_scan_cpu, hm_find_cpu, hm_find_many_cpu, hm_collect_cpu,
-// hm_collect_many_cpu, hm_hash_many_cpu, hm_verify_cpu and hm_verify_many_cpu:
+// hm_collect_many_cpu, hm_hash_many_cpu, hm_verify_cpu, hm_verify_many_cpu and
+// hm_find_k_cpu:
 // the min-hash scan, the first-below-target search (ABI 1.10) and its batch
 // form (ABI 1.13), the all-below-target collection (ABI 1.11) and its batch
 // form (ABI 1.15), the recheck of a list (ABI 1.12) and of the lists of many
-// messages (ABI 1.14), on the host's cores.
+// messages (ABI 1.14) and the k-lowest-below-target search (ABI 1.16), on the
+// host's cores.
 //
 // SURVEY §8(b)'s liveness path.  The reference miner always answers a
 // Request with a Result (cmu440/bitcoin/miner/miner.go:60-62); a GPU miner
@@ -27,6 +29,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <mutex>
 #include <thread>
 #include <utility>
 #include <vector>
@@ -208,6 +211,61 @@ void find_worker(const MsgPlan& mp, uint64_t lo, uint64_t hi, uint64_t target, u
             sh->hit.store(true, std::memory_order_relaxed);
             return true;  // ascending: the window's first hit is its lowest
         });
+    }
+}
+
+// hm_find_k_cpu's shared state.  Threads take ascending windows of kFindWindow
+// nonces from `next`, as find_worker does, and keep a window's hits (the first
+// k at most: a window cannot give the answer more) until its end; then, under
+// `mu`, they join `recs`, which is cut back to its k lowest nonces whenever it
+// holds more.  Once `recs` holds k, `bound` drops to the largest nonce among
+// them: k hits at or below it are known, so windows that start above it are
+// not begun and a window's walk ends at its first nonce above it.  `bound`
+// only decreases, and a window is left out only above a value already in it:
+// every hit at or below the k-th lowest lies in a window that was walked to
+// that hit, whatever the order the threads ran in.
+struct FindKShared {
+    std::atomic<uint64_t> next{0};
+    std::atomic<uint64_t> bound{~0ull};
+    std::mutex mu;
+    std::vector<hm_result> recs;  // under mu
+    bool failed = false;          // under mu: out of memory
+};
+
+void find_k_worker(const MsgPlan& mp, uint64_t lo, uint64_t hi, uint64_t target, size_t k,
+                   uint64_t nwin, CompressFn compress, FindKShared* sh) {
+    const auto by_nonce = [](const hm_result& x, const hm_result& y) { return x.nonce < y.nonce; };
+    std::vector<hm_result> mine;
+    for (;;) {
+        const uint64_t w = sh->next.fetch_add(1, std::memory_order_relaxed);
+        if (w >= nwin) return;
+        const uint64_t a = lo + w * kFindWindow;  // w < nwin: no wrap
+        const uint64_t bound = sh->bound.load(std::memory_order_relaxed);
+        if (a > bound) return;  // so is every later window
+        const uint64_t b = hi - a < kFindWindow - 1 ? hi : a + (kFindWindow - 1);
+        try {
+            mine.clear();
+            walk_chunk(mp, a, b, compress, [&](uint64_t key, uint64_t n) {
+                if (key >= target) return false;
+                if (n > bound) return true;  // ascending: so is the rest of the window
+                mine.push_back(hm_result{key, n});
+                return mine.size() == k;
+            });
+            if (mine.empty()) continue;
+            std::lock_guard<std::mutex> g(sh->mu);
+            sh->recs.insert(sh->recs.end(), mine.begin(), mine.end());
+            if (sh->recs.size() >= k) {
+                std::nth_element(sh->recs.begin(), sh->recs.begin() + (k - 1), sh->recs.end(),
+                                 by_nonce);
+                sh->recs.resize(k);
+                // under mu the k-th lowest nonce held only decreases
+                sh->bound.store(sh->recs[k - 1].nonce, std::memory_order_relaxed);
+            }
+        } catch (...) {
+            std::lock_guard<std::mutex> g(sh->mu);
+            sh->failed = true;
+            return;
+        }
     }
 }
 
@@ -460,6 +518,48 @@ extern "C" int hm_find_cpu(const uint8_t* msg, size_t len, uint64_t lo, uint64_t
             *out = hm_result{~0ull, 0};
             *found = 0;
         }
+        return HM_OK;
+    } catch (const std::bad_alloc&) {
+        return HM_ERR_NOMEM;
+    } catch (...) {
+        return HM_ERR_INTERNAL;
+    }
+}
+
+extern "C" int hm_find_k_cpu(const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
+                             uint64_t target, size_t k, int threads, hm_result* out, size_t* n) {
+    using namespace hm;
+    if (!out || !n || (!msg && len) || k == 0 || k > HM_FIND_K_MAX) return HM_ERR_INVALID;
+    try {
+        if (lo > hi || target == 0) {
+            *n = 0;
+            return HM_OK;
+        }
+        static const uint8_t empty = 0;
+        const MsgPlan mp = plan_message(msg ? msg : &empty, msg ? len : 0);
+        const CompressFn compress = pick_compress();
+        // windows and threads as hm_find_cpu's
+        const uint64_t nwin = (hi - lo) / kFindWindow + 1;
+        unsigned nt = threads > 0 ? (unsigned)threads : default_threads();
+        nt = (unsigned)std::min<uint64_t>(std::min(nt, 1024u), nwin);
+        FindKShared sh;
+        std::vector<std::thread> pool;
+        pool.reserve(nt);
+        for (unsigned t = 0; t + 1 < nt; ++t) {
+            try {
+                pool.emplace_back(find_k_worker, std::cref(mp), lo, hi, target, k, nwin, compress,
+                                  &sh);
+            } catch (...) {  // no thread: the started ones and the caller do the work
+                break;
+            }
+        }
+        find_k_worker(mp, lo, hi, target, k, nwin, compress, &sh);  // the calling thread
+        for (auto& th : pool) th.join();
+        if (sh.failed) return HM_ERR_NOMEM;
+        std::sort(sh.recs.begin(), sh.recs.end(),
+                  [](const hm_result& x, const hm_result& y) { return x.nonce < y.nonce; });
+        if (!sh.recs.empty()) memcpy(out, sh.recs.data(), sh.recs.size() * sizeof(hm_result));
+        *n = sh.recs.size();
         return HM_OK;
     } catch (const std::bad_alloc&) {
         return HM_ERR_NOMEM;

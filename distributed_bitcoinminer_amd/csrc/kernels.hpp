@@ -289,6 +289,41 @@ struct FusedCollectArgs {
 };
 
 // ---------------------------------------------------------------------------
+// hm_find_k (find_k_kernels.hip): the k lowest nonces whose hash
+// is below a target, with hm_find's early exit.  Five 64-bit words per device
+// (`ctl`, indices kFk*), initialised on the stream before a call's first
+// launch, and hm_collect's record buffer of `cap` >= k records.  The find_k
+// kernels take the scan kernel's argument block (cand and sums unused) plus
+// this one.
+// ---------------------------------------------------------------------------
+constexpr int kFkStop = 0;      // MaxUint64; lowered once to a nonce V with k records <= V written
+constexpr int kFkCursor = 1;    // 0; the next free record slot
+constexpr int kFkFilled = 2;    // 0; records in slots < k whose task has published
+constexpr int kFkMaxk = 3;      // 0; the largest nonce among those records
+constexpr int kFkTasksRun = 4;  // 0; += tasks whose hash loop ran, once per wave at exit
+constexpr int kFkWords = 5;
+struct FindKArgs {
+    uint64_t* ctl;       // the device's kFkWords words
+    uint64_t* out;       // cap records of 2 x u64 (hash, nonce)
+    uint64_t target;     // >= 1
+    uint64_t launch_lo;  // the launch's smallest nonce: stop < launch_lo -> exit at once
+    uint32_t cap;        // k <= cap <= HM_COLLECT_CAP_MAX
+    uint32_t k;          // 1 .. HM_FIND_K_MAX
+};
+struct FindKTiledArgs {
+    TiledArgs t;
+    FindKArgs f;
+};
+struct FindKChainedArgs {
+    ChainedArgs c;
+    FindKArgs f;
+};
+struct FindKGenericArgs {
+    GenericArgs g;
+    FindKArgs f;
+};
+
+// ---------------------------------------------------------------------------
 // hm_hash_many / hm_verify (verify_kernels.hip, DESIGN.md "Recheck a list"):
 // Hash(msg, nonce) for a LIST of arbitrary nonces, one element per lane, each
 // lane with its own digit count and tail layout.  hm_hash_list_kernel<false>

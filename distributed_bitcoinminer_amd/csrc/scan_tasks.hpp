@@ -1,6 +1,6 @@
 // scan_tasks.hpp -- one task of each scan kernel kind, shared by the
 // per-segment kernels (scan_kernels.hip, find_kernels.hip,
-// collect_kernels.hip) and the fused small-request kernel
+// collect_kernels.hip, find_k_kernels.hip) and the fused small-request kernel
 // (fused_kernels.hip): the reductions a task folds its nonces into, the task
 // dispenser, the decoding of a task id, the list of tiled layouts and the
 // task bodies.
@@ -142,6 +142,67 @@ DEV void take_step(WaveCollect& c, bool cand, uint32_t h0, uint32_t h1, uint64_t
                         c.out[2 * slot] = key;
                         c.out[2 * slot + 1] = nn;
                     }
+                }
+            }
+        }
+    }
+}
+
+// "The k lowest below target" reduction (find_k_kernels.hip, hm_find_k):
+// WaveCollect's step -- the one compare per nonce, lane_ok, one cursor
+// reservation per step with hits, the `full` rule -- without the count, and
+// with two wave-uniform registers the kernel resets before each task: `c`,
+// how many of the task's records landed in slots below k, and `mx`, the
+// largest nonce among those.  The kernel publishes both after the task; once
+// all k such slots are published their largest nonce bounds the k-th lowest
+// hit and becomes the stop word.
+struct WaveFirstK {
+    uint32_t thi;      // (target - 1) >> 32, target >= 1
+    uint32_t cap;      // records the buffer holds, >= k
+    uint32_t k;
+    uint64_t target;
+    uint64_t* cursor;  // next free slot (agent scope)
+    uint64_t* out;     // 2 x u64 per slot: (hash, nonce)
+    bool full = false;  // a reservation of this wave began at or past cap (uniform)
+    uint32_t c = 0;     // this task's records in slots < k (uniform)
+    uint64_t mx = 0;    // the largest nonce among them (uniform)
+};
+DEV bool wave_cand(const WaveFirstK& f, uint32_t h0) { return h0 <= f.thi; }
+DEV void take_step(WaveFirstK& f, bool cand, uint32_t h0, uint32_t h1, uint64_t nbase,
+                   uint32_t off, uint64_t seg_lo, uint64_t seg_hi, bool lane_ok) {
+    if (__builtin_amdgcn_ballot_w64(cand)) {
+        const uint64_t key = ((uint64_t)h0 << 32) | h1;
+        const uint64_t nn = nbase + off;
+        const bool ok = cand && lane_ok && key < f.target && nn >= seg_lo && nn <= seg_hi;
+        const uint64_t hits = __builtin_amdgcn_ballot_w64(ok);
+        if (hits && !f.full) {
+            const uint32_t n = (uint32_t)__builtin_popcountll(hits);
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi(
+                (uint32_t)(hits >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hits, 0u));
+            uint64_t base = 0;
+            if (ok && rank == 0)
+                base = __hip_atomic_fetch_add(f.cursor, (uint64_t)n, __ATOMIC_RELAXED,
+                                              __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t src = (uint32_t)__builtin_ctzll(hits);
+            base = ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(base >> 32), src) << 32) |
+                   __builtin_amdgcn_readlane((uint32_t)base, src);
+            if (base >= f.cap) {
+                f.full = true;
+            } else {
+                const uint64_t slot = base + rank;
+                if (ok && slot < f.cap) {
+                    f.out[2 * slot] = key;
+                    f.out[2 * slot + 1] = nn;
+                }
+                if (base < f.k) {
+                    // the step's records in slots < k: their count, and their
+                    // largest nonce as the wave minimum of the complements
+                    uint64_t inv = ok && slot < f.k ? ~nn : ~0ull, zero = 0;
+                    wave_min(inv, zero);
+                    const uint64_t m = ~uni64(inv);
+                    if (m > f.mx) f.mx = m;
+                    const uint64_t room = f.k - base;
+                    f.c += n < room ? n : (uint32_t)room;
                 }
             }
         }
@@ -313,8 +374,8 @@ DEV uint64_t lane_digits(uint32_t v, uint32_t q) {
 // t0 runs over [t0_begin, t0_end) (the fused launch's split tasks; the
 // per-segment kernels take the constant defaults, so their loop is the full
 // one).  Best is the reduction the task folds its nonces into: WaveBest (the
-// running minimum, the default), WaveFirst (hm_find) or WaveCollect
-// (hm_collect); each brings its wave_cand (the one compare per nonce) and
+// running minimum, the default), WaveFirst (hm_find), WaveCollect
+// (hm_collect) or WaveFirstK (hm_find_k); each brings its wave_cand (the one compare per nonce) and
 // take_step.
 // ---------------------------------------------------------------------------
 template <int W1, bool STRADDLE, bool TRAILER, bool CSUM, typename S0, typename KW,

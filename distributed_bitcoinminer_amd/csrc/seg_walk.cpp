@@ -11,8 +11,14 @@ KernelName kernel_name(Family family, int kind, const SegPlan* s) {
     static const char* const layouts[] = {"generic", "tiled", "chained", "fused"};
     static const char* const args[] = {"GenericArgs", "TiledArgs", "ChainedArgs", "FusedArgs"};
     const int li = kind == HM_KIND_TILED ? 1 : kind == HM_KIND_CHAINED ? 2 : kind == HM_KIND_FUSED ? 3 : 0;
-    const char* pre = family == Family::Find ? "find_" : family == Family::Collect ? "collect_" : "";
-    const char* arg_pre = family == Family::Find ? "Find" : family == Family::Collect ? "Collect" : "";
+    const char* pre = family == Family::Find      ? "find_"
+                      : family == Family::Collect ? "collect_"
+                      : family == Family::FindK   ? "find_k_"
+                                                  : "";
+    const char* arg_pre = family == Family::Find      ? "Find"
+                          : family == Family::Collect ? "Collect"
+                          : family == Family::FindK   ? "FindK"
+                                                      : "";
     std::string fn = std::string("hm_") + pre + layouts[li] +
                      (family == Family::ScanCsum ? "_csum" : "") + "_kernel";
     std::string arg = std::string(arg_pre) + args[li];

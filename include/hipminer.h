@@ -752,6 +752,79 @@ typedef struct hm_collect_many_stats {
  * hm_collect_many's stats; HM_ERR_INVALID before the first one. */
 int hm_collect_many_stats_sized(const hm_ctx *ctx, hm_collect_many_stats *out, size_t size);
 
+/* ABI 1.16: the next k shares.  A pool-style miner asks "from nonce lo, give
+ * me the next k nonces below the target", over a range that is effectively
+ * open.  Let H be the nonces n of the INCLUSIVE [lo, hi] with
+ * Hash(msg, n) < target (strict '<', as in find and collect), ascending.
+ *   *n = min(k, |H|), and out[0 .. *n) holds the *n LOWEST elements of H as
+ *   (Hash(msg, n), n), ascending by nonce: bit for bit the first *n records
+ *   hm_collect would write.  Nothing at or beyond out[*n] is touched.
+ *   *n <  k: the range is exhausted, every nonce of it was hashed.
+ *   *n == k: the caller resumes at out[k-1].nonce + 1.
+ * k = 1 is hm_find (*n is its found).  target = 0 and lo > hi give *n = 0 and
+ * enqueue nothing.  hi may be UINT64_MAX, and nonce UINT64_MAX is an ordinary
+ * record.  The answer never depends on dispatch order.
+ *
+ * The call stops early inside a launch, as hm_find does, and records as
+ * hm_collect does: waves append their hits to a device buffer
+ * through one cursor; once the first k slots of it are all written, the largest
+ * nonce among them becomes the device's stop word -- k hits at or below it
+ * exist -- and waves skip every task above it.  The host enqueues launches in
+ * ascending order on stream 0, at most four in flight, reads the words back
+ * after each batch, never issues work above the lowest stop word of any device,
+ * and ends the call when nothing unissued lies below it.  It then sorts the
+ * records by nonce and keeps the k lowest, after hm_collect's checks.  With
+ * several devices each seeks k hits in its own shard (hm_find's pieces) and the
+ * host merges the union.  The device buffer holds min(2^24, 2k + 4096) records;
+ * when a dense target overflows it the early exit has still bounded the answer,
+ * and the call takes it exactly from hm_collect's path over ascending windows
+ * of the bounded range (hm_find_k_stats.fallback = 1).
+ *
+ * HM_ERR_INVALID: k == 0, k > HM_FIND_K_MAX, out or n NULL, msg == NULL with
+ * len > 0 (msg == NULL with len == 0 is the empty message).  `out` and `*n` are
+ * written only on HM_OK.  An abandoned context returns HM_ERR_TIMEOUT.
+ * HM_OPT_DEADLINE_MS applies (auto models the whole range, as for hm_find: an
+ * upper bound), HM_OPT_FORCE_GENERIC and HM_OPT_GRID_PER_CU are honoured; the
+ * stream, fused and RCCL options do not apply.  The records go through
+ * hm_collect's device buffer, and each device keeps five more words, made on
+ * first use and kept until hm_close.  The call changes nothing that any other
+ * hm_*_stats* call reports. */
+#define HM_FIND_K_MAX (1u << 20)
+int hm_find_k(hm_ctx *ctx, const uint8_t *msg, size_t len, uint64_t lo, uint64_t hi,
+              uint64_t target, size_t k, hm_result *out, size_t *n);
+
+/* The same answer as hm_find_k on the host's cores, no GPU (`threads` and
+ * windows as hm_find_cpu's).  Threads keep the hits of the windows they walk;
+ * once k are held, windows above the largest of the k lowest are not begun. */
+int hm_find_k_cpu(const uint8_t *msg, size_t len, uint64_t lo, uint64_t hi, uint64_t target,
+                  size_t k, int threads, hm_result *out, size_t *n);
+
+/* Work accounting of the most recent successful hm_find_k on a context.  The
+ * struct only grows at its end. */
+typedef struct hm_find_k_stats {
+    double wall_ms;           /* host wall time of the call                      */
+    double kernel_ms;         /* summed HIP-event time of its launches, the
+                                 overflow path's collect launches included       */
+    uint64_t nonces_enqueued; /* as in hm_find_stats, plus the overflow path's
+                                 windows                                         */
+    uint64_t tasks_total;     /* tasks of the find_k launches issued             */
+    uint64_t tasks_run;       /* tasks whose hash loop ran (the others were
+                                 skipped above the stop word)                    */
+    uint64_t records;         /* records read back from the devices' buffers
+                                 (min(cursor, buffer) summed over devices)       */
+    int32_t launches;         /* find_k launches plus overflow-path launches     */
+    int32_t ndev;             /* devices of the context                          */
+    int32_t found;            /* the call's *n                                   */
+    int32_t fallback;         /* 1: a device's buffer overflowed and the answer
+                                 came from the overflow path; else 0             */
+} hm_find_k_stats;
+#define HM_FIND_K_STATS_SIZE_1_16 64 /* ABI 1.16 */
+
+/* Writes at most `size` bytes (pass sizeof the struct as the caller compiled
+ * it; >= HM_FIND_K_STATS_SIZE_1_16) of the last successful hm_find_k's stats;
+ * HM_ERR_INVALID before the first one. */
+int hm_find_k_stats_sized(const hm_ctx *ctx, hm_find_k_stats *out, size_t size);
+
 int hm_set_option(hm_ctx *ctx, int opt, int64_t value);
 
 const char *hm_strerror(int rc);

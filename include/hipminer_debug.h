@@ -69,6 +69,11 @@ extern "C" {
                                   not fused by hm_collect_many, so a test can
                                   put the fused/unfused boundary at a few
                                   hundred nonces                               */
+#define HM_OPT_FIND_K_BUF 23    /* test hook (1..2^24; 0 = default min(2^24,
+                                  2k + 4096); ABI 1.16): records of the device
+                                  buffer hm_find_k collects into (a call uses
+                                  at least its k), so a test can force the
+                                  overflow path with a few hundred nonces      */
 
 /* The embedded scan code object: *p = its first byte, returns its size.
  * bench.py hashes these bytes to match a PMC summary to the build that runs. */
