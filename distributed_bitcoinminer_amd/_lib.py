@@ -124,6 +124,27 @@ class hm_find_k_stats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class hm_find_k_request(ctypes.Structure):
+    """hm_find_k_request of include/hipminer.h (ABI 1.17)."""
+    _fields_ = [("msg", ctypes.c_char_p), ("len", ctypes.c_size_t),
+                ("lo", ctypes.c_uint64), ("hi", ctypes.c_uint64),
+                ("target", ctypes.c_uint64), ("k", ctypes.c_size_t)]
+
+
+class hm_find_k_many_stats(ctypes.Structure):
+    """hm_find_k_many_stats of include/hipminer.h (ABI 1.17)."""
+    _fields_ = [("wall_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
+                ("nonces_enqueued", ctypes.c_uint64), ("tasks_total", ctypes.c_uint64),
+                ("tasks_run", ctypes.c_uint64), ("records", ctypes.c_uint64),
+                ("found", ctypes.c_uint64), ("requests", ctypes.c_int32),
+                ("fused", ctypes.c_int32), ("fallback", ctypes.c_int32),
+                ("overflow", ctypes.c_int32), ("launches", ctypes.c_int32),
+                ("ndev", ctypes.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class hm_collect_stats(ctypes.Structure):
     """hm_collect_stats of include/hipminer.h (ABI 1.11)."""
     _fields_ = [("wall_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
@@ -288,6 +309,18 @@ def load() -> ctypes.CDLL:
         lib.hm_find_k_stats_sized.restype = ctypes.c_int
         lib.hm_find_k_stats_sized.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_find_k_stats),
                                               ctypes.c_size_t]
+        lib.hm_find_k_many.restype = ctypes.c_int
+        lib.hm_find_k_many.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_find_k_request),
+                                       ctypes.c_int, ctypes.POINTER(hm_result),
+                                       ctypes.POINTER(ctypes.c_size_t)]
+        lib.hm_find_k_many_cpu.restype = ctypes.c_int
+        lib.hm_find_k_many_cpu.argtypes = [ctypes.POINTER(hm_find_k_request), ctypes.c_int,
+                                           ctypes.c_int, ctypes.POINTER(hm_result),
+                                           ctypes.POINTER(ctypes.c_size_t)]
+        lib.hm_find_k_many_stats_sized.restype = ctypes.c_int
+        lib.hm_find_k_many_stats_sized.argtypes = [ctypes.c_void_p,
+                                                   ctypes.POINTER(hm_find_k_many_stats),
+                                                   ctypes.c_size_t]
         lib.hm_collect.restype = ctypes.c_int
         lib.hm_collect.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint64,
                                    ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(hm_result),
@@ -476,6 +509,22 @@ class Context:
             raise HipMinerError(rc, "hm_find_k_stats_sized")
         return st.as_dict()
 
+    def find_k_many(self, requests):
+        """hm_find_k_many (ABI 1.17) over [(msg, lo, hi, target, k), ...]: for
+        each request what Context.find_k returns, a list of (hash, nonce); each
+        request's first 2^27 nonces run as one fused launch that exits early.
+        A msg of None is the empty message passed as a NULL pointer."""
+        return _find_k_many(lambda arr, n, out, counts: self._lib.hm_find_k_many(
+            self._h, arr, n, out, counts), "hm_find_k_many", requests)
+
+    def find_k_many_stats(self) -> dict:
+        """hm_find_k_many_stats_sized: work accounting of the last find_k_many."""
+        st = hm_find_k_many_stats()
+        rc = self._lib.hm_find_k_many_stats_sized(self._h, ctypes.byref(st), ctypes.sizeof(st))
+        if rc != HM_OK:
+            raise HipMinerError(rc, "hm_find_k_many_stats_sized")
+        return st.as_dict()
+
     def collect(self, msg, lo: int, hi: int, target: int, cap: int):
         """hm_collect (ABI 1.11): (total, records).  total = the number of
         nonces in the inclusive [lo, hi] whose hash is below `target`, always
@@ -661,6 +710,46 @@ def find_k_cpu(msg, lo: int, hi: int, target: int, k: int, threads: int = 0):
     """hm_find_k_cpu (ABI 1.16): Context.find_k's answer on the host's cores."""
     return _find_k(lambda m, out, n: load().hm_find_k_cpu(
         m, len(m), lo, hi, target, k, threads, out, n), "hm_find_k_cpu", msg, k)
+
+
+def find_k_requests(requests):
+    """[(msg, lo, hi, target, k), ...] as an hm_find_k_request array: (array,
+    n, the byte strings the array borrows -- keep them alive for the call).  A
+    msg of None becomes a NULL pointer with len 0."""
+    reqs = list(requests)
+    n = len(reqs)
+    keep = [None if r[0] is None else as_bytes(r[0]) for r in reqs]
+    arr = (hm_find_k_request * max(1, n))()
+    for i, ((_, lo, hi, target, k), m) in enumerate(zip(reqs, keep)):
+        arr[i] = hm_find_k_request(m, len(m) if m is not None else 0, lo, hi, target, k)
+    return arr, n, keep
+
+
+def _find_k_many(call, what: str, requests):
+    """Run a find_k_many entry point with one buffer of sum(k) records and
+    shape its answers: a list of lists of (hash, nonce)."""
+    arr, n, keep = find_k_requests(requests)
+    ks = [int(arr[i].k) for i in range(n)]
+    valid = all(0 < k <= HM_FIND_K_MAX for k in ks)
+    buf = (hm_result * max(1, sum(ks)))() if valid else (hm_result * 1)()
+    counts = (ctypes.c_size_t * max(1, n))()
+    rc = call(arr, n, buf, counts)
+    del keep
+    if rc != HM_OK:
+        raise HipMinerError(rc, what)
+    out, off = [], 0
+    for i in range(n):
+        c = int(counts[i])
+        words = struct.unpack_from(f"={2 * c}Q", buf, 16 * off) if c else ()
+        out.append(list(zip(words[0::2], words[1::2])))
+        off += ks[i]
+    return out
+
+
+def find_k_many_cpu(requests, threads: int = 0):
+    """hm_find_k_many_cpu (ABI 1.17): Context.find_k_many's answers on the host's cores."""
+    return _find_k_many(lambda arr, n, out, counts: load().hm_find_k_many_cpu(
+        arr, n, threads, out, counts), "hm_find_k_many_cpu", requests)
 
 
 def _collect(call, what: str, msg, cap: int):

@@ -28,6 +28,8 @@
 //   fused_collect_kernels.hip per request, hm_collect's path for the rest.
 //   hm_find_k (ABI 1.16): find_k.cpp over hm_find's walk, the kernels of
 //   find_k_kernels.hip, hm_collect's path when its record buffer overflows.
+//   hm_find_k_many (ABI 1.17): find_k_many.cpp, one fused launch of
+//   fused_find_k_kernels.hip per request, hm_find_k's path for what is left.
 //   The scan kernels come from their own code object (scan_kernels.hip ->
 //   align_loops.py -> hipminer_scan.hsaco, embedded by scan_blob.S), loaded
 //   per device with hipModuleLoadData and launched with hipModuleLaunchKernel.
@@ -64,7 +66,8 @@ uint64_t hm_hash(const uint8_t* msg, size_t len, uint64_t nonce) {
 // 1.14: hm_verify_many, hm_verify_many_cpu, hm_verify_many_stats_sized, HM_OPT_VERIFY_JOBS
 // 1.15: hm_collect_many, hm_collect_many_cpu, hm_collect_many_stats_sized, HM_OPT_COLLECT_WINDOW
 // 1.16: hm_find_k, hm_find_k_cpu, hm_find_k_stats_sized, HM_OPT_FIND_K_BUF
-int hm_version(void) { return (1 << 16) | 16; }
+// 1.17: hm_find_k_many, hm_find_k_many_cpu, hm_find_k_many_stats_sized
+int hm_version(void) { return (1 << 16) | 17; }
 
 // The digest of the sources this library was built from (build_id.py), kept
 // in the binary behind a tag so tools can read it without loading the library.
@@ -313,6 +316,35 @@ int hm_find_k_stats_sized(const hm_ctx* ctx, hm_find_k_stats* out, size_t size) 
     std::lock_guard<std::mutex> g(ctx->mu);
     if (!ctx->have_find_k_stats) return HM_ERR_INVALID;
     memcpy(out, &ctx->last_find_k, std::min(size, sizeof(hm_find_k_stats)));
+    return HM_OK;
+}
+
+int hm_find_k_many(hm_ctx* ctx, const hm_find_k_request* reqs, int n, hm_result* out,
+                   size_t* counts) {
+    if (!ctx || n < 0 || (n > 0 && (!reqs || !out || !counts))) return HM_ERR_INVALID;
+    for (int r = 0; r < n; ++r)
+        if ((!reqs[r].msg && reqs[r].len) || reqs[r].k == 0 || reqs[r].k > HM_FIND_K_MAX)
+            return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    std::vector<std::vector<hm_result>> recs;
+    int rc = guarded([&] { return find_k_many_locked(ctx, reqs, n, &recs); });
+    if (rc) return rc;
+    // all n answers, or (on any failure above) none; inside request i's slot
+    // nothing at or beyond its counts[i] records is touched
+    size_t off = 0;
+    for (int r = 0; r < n; ++r) {
+        if (!recs[r].empty()) memcpy(out + off, recs[r].data(), recs[r].size() * sizeof(hm_result));
+        counts[r] = recs[r].size();
+        off += reqs[r].k;
+    }
+    return HM_OK;
+}
+
+int hm_find_k_many_stats_sized(const hm_ctx* ctx, hm_find_k_many_stats* out, size_t size) {
+    if (!ctx || !out || size < HM_FIND_K_MANY_STATS_SIZE_1_17) return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!ctx->have_find_k_many_stats) return HM_ERR_INVALID;
+    memcpy(out, &ctx->last_find_k_many, std::min(size, sizeof(hm_find_k_many_stats)));
     return HM_OK;
 }
 

@@ -105,6 +105,7 @@ void device_free(Device& dv) {
     if (dv.find_ctl) (void)hipFree(dv.find_ctl);
     if (dv.find_many_ctl) (void)hipFree(dv.find_many_ctl);
     if (dv.find_k_ctl) (void)hipFree(dv.find_k_ctl);
+    if (dv.find_k_many_ctl) (void)hipFree(dv.find_k_many_ctl);
     if (dv.collect_ctl) (void)hipFree(dv.collect_ctl);
     if (dv.collect_buf) (void)hipFree(dv.collect_buf);
     if (dv.collect_many_ctl) (void)hipFree(dv.collect_many_ctl);

@@ -66,16 +66,13 @@ int find_k_windows(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint
 
 }  // namespace
 
-// hm_find_k with ctx->mu held.
-int find_k_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
-                  uint64_t target, size_t k, std::vector<hm_result>* recs) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const uint8_t* m;
-    size_t mlen;
-    int rc = begin_ranged_call(ctx, msg, len, lo, hi, t0, &m, &mlen);
-    if (rc) return rc;
+// hm_find_k without its opening and its stats (hm_find_k_many's fallback
+// takes this path too).
+int find_k_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_t hi,
+                uint64_t target, size_t k, FindKTally* out, std::vector<hm_result>* recs) {
+    int rc = HM_OK;
     const int ndev = (int)ctx->devs.size();
-    FindTally tally;
+    FindTally& tally = out->t;
     uint64_t records = 0;
     bool overflow = false;
     uint64_t best = ~0ull;
@@ -179,6 +176,26 @@ int find_k_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint
                 return HM_ERR_INTERNAL;
         }
     }
+    out->records += records;
+    out->overflow = out->overflow || overflow;
+    return HM_OK;
+}
+
+// hm_find_k with ctx->mu held.
+int find_k_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
+                  uint64_t target, size_t k, std::vector<hm_result>* recs) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint8_t* m;
+    size_t mlen;
+    int rc = begin_ranged_call(ctx, msg, len, lo, hi, t0, &m, &mlen);
+    if (rc) return rc;
+    const int ndev = (int)ctx->devs.size();
+    FindKTally kt;
+    rc = find_k_core(ctx, m, mlen, lo, hi, target, k, &kt, recs);
+    if (rc) return rc;
+    const FindTally& tally = kt.t;
+    const uint64_t records = kt.records;
+    const bool overflow = kt.overflow;
     hm_find_k_stats st{};
     st.kernel_ms = tally.kernel_ms;
     st.nonces_enqueued = tally.nonces;

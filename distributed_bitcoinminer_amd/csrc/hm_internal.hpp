@@ -8,6 +8,7 @@
 //   find.cpp      hm_find
 //   find_many.cpp hm_find_many
 //   find_k.cpp    hm_find_k
+//   find_k_many.cpp hm_find_k_many
 //   collect.cpp   hm_collect
 //   collect_many.cpp hm_collect_many
 //   verify.cpp    hm_hash_many, hm_verify
@@ -120,6 +121,9 @@ struct Device {
     // hm_find_k, made on first use: the kFkWords control words (kernels.hpp FindKArgs).  The
     // records go through collect_buf, which hm_collect and this call never use at once
     uint64_t* find_k_ctl = nullptr;
+    // hm_find_k_many, made on first use: [kMaxBatch][kFkWords], the control words of request r of
+    // a chunk.  The requests' record slices are laid side by side in collect_buf
+    uint64_t* find_k_many_ctl = nullptr;
     // hm_collect: [0] total, [1] slot cursor (kernels.hpp CollectArgs), and the record buffer of
     // collect_cap records, grown when a larger cap arrives (the old one joins `retired`)
     uint64_t* collect_ctl = nullptr;
@@ -231,6 +235,8 @@ struct hm_ctx {
     hm_collect_many_stats last_collect_many{};
     bool have_find_k_stats = false;  // and hm_find_k
     hm_find_k_stats last_find_k{};
+    bool have_find_k_many_stats = false;  // and hm_find_k_many
+    hm_find_k_many_stats last_find_k_many{};
 };
 
 namespace hm {
@@ -506,7 +512,20 @@ int find_issue(hm_ctx* ctx, Device& dv, FindDev& fd, const MsgPlan& mp, Family f
 int find_collect(hm_ctx* ctx, Device& dv, FindDev& fd, FindTally& tally, const uint64_t* dev_ctl,
                  int nwords);
 
-// ---- find_many.cpp: shared with collect_many.cpp ----
+// ---- find_k.cpp: hm_find_k without its opening and its stats, for hm_find_k_many's fallback ----
+struct FindKTally {
+    FindTally t;           // launches, tasks and kernel time, the overflow path's included
+    uint64_t records = 0;  // records read back (min(cursor, buffer) summed over devices)
+    bool overflow = false; // a device's buffer overflowed: the answer came from the overflow path
+};
+// The k lowest hits of [lo, hi], on stream 0 through the per-segment find_k
+// kernels: *recs as hm_find_k returns it, the work added to *tally.  The
+// call's deadline is already set; on failure the streams are drained
+// (drain_failed).
+int find_k_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_t hi,
+                uint64_t target, size_t k, FindKTally* tally, std::vector<hm_result>* recs);
+
+// ---- find_many.cpp: shared with collect_many.cpp and find_k_many.cpp ----
 // A batch call that fails with rc leaves nothing queued: unless rc is a
 // timeout, every stream the devices have made is waited for, then
 // drain_failed (stream 0 and the events).  Returns rc.
@@ -545,6 +564,9 @@ int find_k_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint
 int collect_many_locked(hm_ctx* ctx, const hm_collect_request* reqs, int n, size_t cap,
                         std::vector<uint64_t>* totals, std::vector<hm_result>* recs,
                         uint64_t* total);
+// hm_find_k_many: (*recs)[i] = what find_k_locked gives for reqs[i], i < n.
+int find_k_many_locked(hm_ctx* ctx, const hm_find_k_request* reqs, int n,
+                       std::vector<std::vector<hm_result>>* recs);
 // hm_hash_many (recs null: `list` holds n nonces, *out gets the n hashes) and
 // hm_verify (recs: n records; *out gets the bad indices, ascending, when
 // *bad <= cap and stays empty otherwise).

@@ -596,6 +596,41 @@ extern "C" int hm_find_many_cpu(const hm_find_request* reqs, int n, int threads,
     }
 }
 
+// hm_find_k_many's answers on the host (ABI 1.17): hm_find_k_cpu request by
+// request; all outputs are written, or none.
+extern "C" int hm_find_k_many_cpu(const hm_find_k_request* reqs, int n, int threads,
+                                  hm_result* out, size_t* counts) {
+    if (n < 0 || (n > 0 && (!reqs || !out || !counts))) return HM_ERR_INVALID;
+    for (int r = 0; r < n; ++r)
+        if ((!reqs[r].msg && reqs[r].len) || reqs[r].k == 0 || reqs[r].k > HM_FIND_K_MAX)
+            return HM_ERR_INVALID;
+    try {
+        std::vector<std::vector<hm_result>> res((size_t)n);
+        for (int r = 0; r < n; ++r) {
+            const hm_find_k_request& q = reqs[r];
+            // one buffer of k records at a time: what is kept is the hits
+            std::vector<hm_result> buf(q.k);
+            size_t got = 0;
+            const int rc = hm_find_k_cpu(q.msg, q.msg ? q.len : 0, q.lo, q.hi, q.target, q.k,
+                                         threads, buf.data(), &got);
+            if (rc) return rc;
+            res[r].assign(buf.begin(), buf.begin() + got);
+        }
+        size_t off = 0;
+        for (int r = 0; r < n; ++r) {
+            if (!res[r].empty())
+                memcpy(out + off, res[r].data(), res[r].size() * sizeof(hm_result));
+            counts[r] = res[r].size();
+            off += reqs[r].k;
+        }
+        return HM_OK;
+    } catch (const std::bad_alloc&) {
+        return HM_ERR_NOMEM;
+    } catch (...) {
+        return HM_ERR_INTERNAL;
+    }
+}
+
 extern "C" int hm_collect_cpu(const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
                               uint64_t target, int threads, hm_result* out, size_t cap,
                               uint64_t* total) {

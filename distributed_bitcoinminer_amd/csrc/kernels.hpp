@@ -322,6 +322,18 @@ struct FindKGenericArgs {
     GenericArgs g;
     FindKArgs f;
 };
+// hm_find_k_many (fused_find_k_kernels.hip): one request's
+// window, every segment in one launch.  `f.ctl` is the REQUEST's kFkWords
+// words -- (stop, cursor) seeded (MaxUint64, 0) by the planner launch
+// (FusedPlanArgs::result), the other three zeroed on the stream before it --
+// and `f.out` the request's own slice of `f.cap` records.  a.cand, a.sums,
+// a.flags and a.trace are unused and f.launch_lo is not read (`stop` is
+// MaxUint64 when the launch starts).
+struct FusedFindKArgs {
+    FusedArgs a;
+    FindKArgs f;
+};
+static_assert(kFkCursor == kFkStop + 1, "the planner's (MaxUint64, 0) seed serves stop and cursor");
 
 // ---------------------------------------------------------------------------
 // hm_hash_many / hm_verify (verify_kernels.hip, DESIGN.md "Recheck a list"):

@@ -30,6 +30,10 @@ KernelName kernel_name(Family family, int kind, const SegPlan* s) {
         fn = "hm_fused_collect_kernel";
         arg = "FusedCollectArgs";
     }
+    if (family == Family::FindK && kind == HM_KIND_FUSED) {  // fused_find_k_kernels.hip
+        fn = "hm_fused_find_k_kernel";
+        arg = "FusedFindKArgs";
+    }
     char targs[48] = "", shown[48] = "";
     if (kind == HM_KIND_TILED) {  // hm_*tiled*_kernel<W1, STRADDLE, TRAILER>
         snprintf(targs, sizeof targs, "ILi%dELb%dELb%dEEEv", s->W1, s->straddle ? 1 : 0,

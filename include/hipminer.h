@@ -825,6 +825,83 @@ typedef struct hm_find_k_stats {
  * HM_ERR_INVALID before the first one. */
 int hm_find_k_stats_sized(const hm_ctx *ctx, hm_find_k_stats *out, size_t size);
 
+/* ABI 1.17: a batch of hm_find_k calls.  A pool-style caller holds many jobs,
+ * usually one message per client, and wants the next k shares of each; at the
+ * targets such callers use hm_find_k is bound by its launches and host round
+ * trips, so a loop over it is too.
+ *   off_i = the sum of reqs[j].k for j < i; request i owns out[off_i .. off_i +
+ *   k_i).  counts[i] and out[off_i .. off_i + counts[i]) are exactly what
+ *   hm_find_k(reqs[i]) returns in *n and out, bit for bit, ascending by nonce.
+ *   Nothing at or beyond out[off_i + counts[i]] inside the request's slot is
+ *   touched.  counts[i] < k_i: that request's range is exhausted.
+ * target = 0 and lo > hi give 0 and enqueue nothing.  hi may be UINT64_MAX, and
+ * nonce UINT64_MAX is an ordinary record.  n == 0 is HM_OK and enqueues nothing.
+ * Outputs are written only on HM_OK, all n requests or none.  The answer never
+ * depends on dispatch order.
+ *
+ * Each request's first 2^27 nonces run as ONE fused launch that records as
+ * hm_find_k does and exits early: the request has its own five
+ * control words and its own slice of min(2^24, 2k + 4096) records, request r
+ * goes whole to device r mod ndev and round-robins over that device's streams,
+ * and every request of a chunk (at most 64 requests, and at most 2^24 records
+ * of slices per device) is enqueued on every device before the host waits on
+ * any.  A request whose window holds fewer than k hits and whose range goes on
+ * continues from the first nonce not fused through hm_find_k's per-segment
+ * path, for the hits still missing; one whose launch overran its slice takes
+ * that path whole.
+ *
+ * HM_ERR_INVALID: n < 0; n > 0 with reqs, out or counts NULL; a request with
+ * k == 0 or k > HM_FIND_K_MAX, or with msg == NULL and len > 0 (msg == NULL
+ * with len == 0 is the empty message).  An abandoned context returns
+ * HM_ERR_TIMEOUT.  HM_OPT_DEADLINE_MS covers the whole call; HM_OPT_FORCE_GENERIC,
+ * HM_OPT_GRID_PER_CU and HM_OPT_STREAMS are honoured as in hm_find_many;
+ * HM_OPT_FUSED = 0 sends every request down the per-segment path.  The slices
+ * share hm_collect's device buffer, and each device keeps 64 x 5 more words,
+ * made on first use and kept until hm_close.  The call changes nothing that any
+ * other hm_*_stats* call reports. */
+typedef struct hm_find_k_request {
+    const uint8_t *msg; size_t len;   /* msg may be NULL when len == 0 */
+    uint64_t lo, hi;                  /* inclusive */
+    uint64_t target;
+    size_t k;                         /* 1 .. HM_FIND_K_MAX */
+} hm_find_k_request;
+
+int hm_find_k_many(hm_ctx *ctx, const hm_find_k_request *reqs, int n, hm_result *out,
+                   size_t *counts);
+
+/* The same answers on the host's cores, no GPU: hm_find_k_cpu request by
+ * request; all outputs are written, or none. */
+int hm_find_k_many_cpu(const hm_find_k_request *reqs, int n, int threads, hm_result *out,
+                       size_t *counts);
+
+/* Work accounting of the most recent successful hm_find_k_many on a context.
+ * The struct only grows at its end. */
+typedef struct hm_find_k_many_stats {
+    double wall_ms;           /* host wall time of the call                      */
+    double kernel_ms;         /* summed HIP-event time of its launches           */
+    uint64_t nonces_enqueued; /* nonces of the launches issued                   */
+    uint64_t tasks_total;     /* tasks of those launches                         */
+    uint64_t tasks_run;       /* tasks whose hash loop ran (the others were
+                                 skipped above a stop word)                      */
+    uint64_t records;         /* records read back from the devices              */
+    uint64_t found;           /* the sum of counts                               */
+    int32_t requests;         /* n                                               */
+    int32_t fused;            /* requests answered by their fused launch alone   */
+    int32_t fallback;         /* requests that needed the per-segment path for
+                                 any reason.  A request that enqueues nothing
+                                 (lo > hi, target = 0) counts in neither         */
+    int32_t overflow;         /* of those, requests whose fused launch overran
+                                 its slice                                       */
+    int32_t launches;         /* fused launches plus fallback launches           */
+    int32_t ndev;             /* devices of the context                          */
+} hm_find_k_many_stats;
+#define HM_FIND_K_MANY_STATS_SIZE_1_17 80 /* ABI 1.17 */
+
+/* Writes at most `size` bytes (pass sizeof the struct as the caller compiled
+ * it; >= HM_FIND_K_MANY_STATS_SIZE_1_17) of the last successful
+ * hm_find_k_many's stats; HM_ERR_INVALID before the first one. */
+int hm_find_k_many_stats_sized(const hm_ctx *ctx, hm_find_k_many_stats *out, size_t size);
+
 int hm_set_option(hm_ctx *ctx, int opt, int64_t value);
 
 const char *hm_strerror(int rc);
