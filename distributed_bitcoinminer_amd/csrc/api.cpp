@@ -30,6 +30,9 @@
 //   find_k_kernels.hip, hm_collect's path when its record buffer overflows.
 //   hm_find_k_many (ABI 1.17): find_k_many.cpp, one fused launch of
 //   fused_find_k_kernels.hip per request, hm_find_k's path for what is left.
+//   The three *_many calls above share one chunk runner on the host
+//   (batch.cpp); fused_tasks.hpp has the fused batch kernels' task walker
+//   (hm_fused_find_kernel runs on it).
 //   The scan kernels come from their own code object (scan_kernels.hip ->
 //   align_loops.py -> hipminer_scan.hsaco, embedded by scan_blob.S), loaded
 //   per device with hipModuleLoadData and launched with hipModuleLaunchKernel.

@@ -47,6 +47,20 @@ int collect_buffer(Device& dv, size_t cap) {
     return HM_OK;
 }
 
+// Slots are handed out in dispatch order, the answer is in nonce order: sort,
+// then every record is distinct, inside [lo, hi] and below the target.
+int sort_check_records(std::vector<hm_result>* recs, uint64_t lo, uint64_t hi, uint64_t target) {
+    std::sort(recs->begin(), recs->end(),
+              [](const hm_result& x, const hm_result& y) { return x.nonce < y.nonce; });
+    for (size_t i = 0; i < recs->size(); ++i) {
+        const hm_result& r = (*recs)[i];
+        if (r.hash >= target || r.nonce < lo || r.nonce > hi ||
+            (i > 0 && r.nonce == (*recs)[i - 1].nonce))
+            return HM_ERR_INTERNAL;
+    }
+    return HM_OK;
+}
+
 namespace {
 
 // Enqueue every launch of segment s on dv's stream 0 (the device's first
@@ -162,15 +176,8 @@ int collect_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64
                 if (rc) return rc;
                 at += (size_t)dev_total[i];
             }
-            // slots are handed out in dispatch order: the answer is in nonce order
-            std::sort(recs->begin(), recs->end(),
-                      [](const hm_result& x, const hm_result& y) { return x.nonce < y.nonce; });
-            for (size_t i = 0; i < recs->size(); ++i) {
-                const hm_result& r = (*recs)[i];
-                if (r.hash >= target || r.nonce < lo || r.nonce > hi ||
-                    (i > 0 && r.nonce == (*recs)[i - 1].nonce))
-                    return HM_ERR_INTERNAL;
-            }
+            rc = sort_check_records(recs, lo, hi, target);
+            if (rc) return rc;
         }
     }
     tally->kernel_ms += kernel_ms;

@@ -31,8 +31,6 @@
 namespace hm {
 namespace {
 
-bool by_nonce(const hm_result& x, const hm_result& y) { return x.nonce < y.nonce; }
-
 // The k lowest hits of [lo, hi] through hm_collect's path, window by window.
 int find_k_windows(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_t hi,
                    uint64_t target, size_t k, CollectTally* tally, std::vector<hm_result>* recs) {
@@ -162,14 +160,8 @@ int find_k_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_
             tally.launches += ct.launches;
             tally.kernel_ms += ct.kernel_ms;
         } else {
-            // slots are handed out in dispatch order: the answer is in nonce order
-            std::sort(recs->begin(), recs->end(), by_nonce);
-            for (size_t i = 0; i < recs->size(); ++i) {
-                const hm_result& r = (*recs)[i];
-                if (r.hash >= target || r.nonce < lo || r.nonce > hi ||
-                    (i > 0 && r.nonce == (*recs)[i - 1].nonce))
-                    return HM_ERR_INTERNAL;
-            }
+            rc = sort_check_records(recs, lo, hi, target);
+            if (rc) return rc;
             if (recs->size() > k) recs->resize(k);
             // a lowered stop word promises k records at or below it
             if (best != ~0ull && (recs->size() < k || recs->back().nonce > best))

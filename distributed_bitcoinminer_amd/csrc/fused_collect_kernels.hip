@@ -57,10 +57,13 @@
 // Which slot a record lands in depends on dispatch order; the host groups the
 // records by tag and sorts each group by nonce, so the answer does not.
 //
-// The task decoders below are this file's own, templates over the reduction
-// (they depend on neither WaveBest nor WaveFirst); fused_kernels.hip and
-// fused_find_kernels.hip keep theirs, so the shipped kernels' text is held
-// byte for byte.
+// The task decoders and the task loop below are this file's own, templates
+// over the reduction.  fused_find_kernels.hip and fused_find_k_kernels.hip take
+// theirs from fused_tasks.hpp; this kernel does not, because on that header it
+// measured 8-9 % slower on a single 120-B request of 10^7 nonces (and 4-8 %
+// faster on batches of 8 and 64: profiles/README.md, batch_dedup/), so its
+// text is held byte for byte.  A change to the walk (the slot-then-counter
+// order, the guided-tail split, the segment lookup) has to be made here too.
 //
 // Compiled like scan_kernels.hip (device-only -S, align_loops.py, linked last
 // into hipminer_scan.hsaco) and looked up by mangled name (kernel_name() in

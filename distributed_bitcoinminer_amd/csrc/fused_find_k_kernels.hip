@@ -86,10 +86,13 @@
 // (find_k_many.cpp).  A published maxk of MaxUint64 leaves `stop` as it is, so
 // the top nonce is an ordinary record.
 //
-// The task decoders and the protocol helpers below are this file's own copies
-// of fused_find_kernels.hip's and find_k_kernels.hip's (those read their
-// argument blocks by value; this kernel reads its own in place): the shipped
-// kernels' text is held byte for byte.
+// The task decoders, the task loop and the protocol helpers below are this
+// file's own copies of fused_tasks.hpp's (which hm_fused_find_kernel runs on)
+// and of find_k_kernels.hip's.  On fused_tasks.hpp this kernel gives the same
+// answers (88 VGPRs against 87, the same occupancy), but its rates were not
+// shown to lie inside the parent's (profiles/README.md, batch_dedup/), so its
+// text is held byte for byte.  A change to the walk or to the leave rule has
+// to be made here too.
 //
 // Compiled like scan_kernels.hip (device-only -S, align_loops.py, linked into
 // hipminer_scan.hsaco) and looked up by mangled name (kernel_name() in

@@ -6,10 +6,11 @@
 //   seg_walk.cpp  one segment -> its sequence of launches (SegWalk), the argument fillers
 //   scan.cpp      hm_scan_many: batching, the fused launch, merge, stats
 //   find.cpp      hm_find
-//   find_many.cpp hm_find_many
 //   find_k.cpp    hm_find_k
-//   find_k_many.cpp hm_find_k_many
 //   collect.cpp   hm_collect
+//   batch.cpp     the chunk runner of the three batch calls below: plan, prepare, launch, wait and read
+//   find_many.cpp hm_find_many
+//   find_k_many.cpp hm_find_k_many
 //   collect_many.cpp hm_collect_many
 //   verify.cpp    hm_hash_many, hm_verify
 //   verify_many.cpp hm_verify_many
@@ -130,9 +131,9 @@ struct Device {
     uint64_t* collect_buf = nullptr;
     size_t collect_cap = 0;
     // hm_collect_many, made on first use: [0] the chunk's slot cursor, [1 + r] request r's total
-    // (kMaxBatch + 1 words); the tag buffer of collect_tags_cap words (the request of each record
-    // slot), grown like collect_buf.  The records go through collect_buf, which hm_collect and
-    // this call never use at once
+    // (kMaxBatch + 1 words); the tag buffer of collect_tags_cap 32-bit words (the request of each
+    // record slot), grown like collect_buf (grow_buffer).  The records go through collect_buf,
+    // which hm_collect and this call never use at once
     uint64_t* collect_many_ctl = nullptr;
     uint32_t* collect_tags = nullptr;
     size_t collect_tags_cap = 0;
@@ -434,7 +435,7 @@ int begin_ranged_call(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, 
 // a scan.  Returns rc.
 int drain_failed(hm_ctx* ctx, int rc);
 
-// ---- scan.cpp: the fused launch, shared with find_many.cpp and collect_many.cpp ----
+// ---- scan.cpp: the fused launch, shared with batch.cpp ----
 bool fusible(const std::vector<SegPlan>& segs);
 // The task order of a fused launch without an early exit: costliest layout
 // first, larger segments first (the launch ends on its cheapest tasks).
@@ -525,12 +526,6 @@ struct FindKTally {
 int find_k_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_t hi,
                 uint64_t target, size_t k, FindKTally* tally, std::vector<hm_result>* recs);
 
-// ---- find_many.cpp: shared with collect_many.cpp and find_k_many.cpp ----
-// A batch call that fails with rc leaves nothing queued: unless rc is a
-// timeout, every stream the devices have made is waited for, then
-// drain_failed (stream 0 and the events).  Returns rc.
-int drain_streams(hm_ctx* ctx, int rc);
-
 // ---- collect.cpp: hm_collect without its opening and its stats, for hm_collect_many's fallback ----
 struct CollectTally {
     uint64_t nonces = 0;
@@ -546,6 +541,126 @@ int collect_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64
 // Make dv's record buffer hold `cap` records (grown by at least doubling, the
 // old one retired).
 int collect_buffer(Device& dv, size_t cap);
+// Records as a device handed them out, in dispatch order: sorted by nonce, then
+// HM_ERR_INTERNAL on a duplicate, a nonce outside [lo, hi] or a hash at or
+// above target.
+int sort_check_records(std::vector<hm_result>* recs, uint64_t lo, uint64_t hi, uint64_t target);
+
+// ---- batch.cpp: one chunk of hm_find_many, hm_collect_many or hm_find_k_many ----
+// One request of a chunk.
+struct BatchReq {
+    const uint8_t* m;  // a null message is the empty one
+    size_t mlen;
+    bool live = false;      // lo <= hi and target != 0: something to hash
+    bool launched = false;  // its fused launch was enqueued
+    uint64_t fused_hi = 0;  // launched: the last nonce of the launch
+    int dev = 0;            // (index0 + r) mod ndev
+    MsgPlan mp;
+    std::vector<SegPlan> segs;  // what its fused launch holds; none: not fused
+    hipEvent_t a = nullptr, b = nullptr;
+};
+// A chunk of at most kMaxBatch requests, from planning to readback.  The
+// family's file drives it: add() per request, prepare(), launch(), finish();
+// what lies between and after them (buffers, answers, fallbacks) is the
+// family's own.  Every device is enqueued before the host waits on any.
+struct BatchChunk {
+    // Requests index0.. of the call; a fused launch holds at most `window`
+    // nonces.  whole = false (an early-exit family): the longest prefix of the
+    // window's segments, ascending by nonce, that fusible() accepts.  whole =
+    // true: a request of at most `window` nonces all of whose segments
+    // fusible() accepts, in fused_order; any other request is not fused.
+    BatchChunk(hm_ctx* ctx, int index0, uint64_t window, bool whole);
+    // Plan the chunk's next request.
+    BatchReq& add(const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, uint64_t target);
+    // The streams device i's launches round-robin over.
+    int used(int i) const { return std::min(nstreams, nfused[i]); }
+    // Each device with a launch: its control block Device::*ctl of `words`
+    // words (made on first use) and its streams.
+    int prepare(uint64_t* Device::*ctl, size_t words);
+    // Enqueue every fused request, each on its device's next stream: the
+    // planner, then the family's fused kernel `name` on an Args block, between the
+    // request's two events.  fill(r, R, dv, stream, &fl, &ka) sets the planner's
+    // outputs (fl.pa.result / acc / n_acc) and ka but ka.a, and may enqueue
+    // onto the stream what must precede the planner.  The launches' nonces,
+    // tasks and count are added to *tally.
+    template <typename Args, typename Fill>
+    int launch(const KernelName& name, FindTally* tally, Fill&& fill);
+    // Wait for every used stream of every device, then read the first `words`
+    // words of each device's control block into ctl[i]; the launches' event
+    // times are added to tally->kernel_ms and the events are free again.
+    int finish(uint64_t* Device::*ctl, size_t words, FindTally* tally);
+
+    hm_ctx* ctx;
+    int index0, ndev, nstreams;
+    uint64_t window;
+    bool whole;
+    std::vector<BatchReq> rq;
+    std::vector<int> nfused;                 // per device: requests with a launch
+    std::vector<std::vector<uint64_t>> ctl;  // per device: the control words read back
+
+private:
+    // Request r's stream and plan; *fn = the family's kernel.
+    int plan_launch(int r, const std::string& symbol, int* si, FusedLaunch* fl,
+                    const Device::Fn** fn);
+    std::vector<int> rr;  // per device: launches so far
+};
+
+template <typename Args, typename Fill>
+int BatchChunk::launch(const KernelName& name, FindTally* tally, Fill&& fill) {
+    for (int r = 0; r < (int)rq.size(); ++r) {
+        BatchReq& R = rq[r];
+        if (R.segs.empty()) continue;
+        Device& dv = ctx->devs[R.dev];
+        int si;
+        FusedLaunch fl;
+        const Device::Fn* fn = nullptr;
+        int rc = plan_launch(r, name.symbol, &si, &fl, &fn);
+        if (rc) return rc;
+        hipStream_t s = dv.stream[si];
+        Args ka;
+        rc = fill(r, R, dv, s, &fl, &ka);
+        if (rc) return rc;
+        ka.a = fl.fa;
+        HIPCHK(launch_fused_plan(fl.pa, s));
+        HIPCHK(hipEventRecord(R.a, s));
+        rc = launch_scan(*fn, ka, fl.grid, s);
+        if (rc) return rc;
+        HIPCHK(hipEventRecord(R.b, s));
+        R.launched = true;
+        R.fused_hi = R.segs.back().hi;
+        tally->nonces += fl.nonces;
+        tally->tasks += fl.fa.ntasks;
+        ++tally->launches;
+    }
+    return HM_OK;
+}
+
+// The opening of a batch call that began at t0: refuses an abandoned context,
+// sets the call's deadline over every request's whole range, frees the events.
+template <typename Req>
+int batch_open(hm_ctx* ctx, const Req* reqs, int n, std::chrono::steady_clock::time_point t0) {
+    // an abandoned context's devices may still run its timed-out work
+    if (ctx->abandoned) return HM_ERR_TIMEOUT;
+    // auto: the floor once, the slack times every request's whole range
+    std::vector<hm_request> whole(n);
+    for (int r = 0; r < n; ++r)
+        whole[r] = hm_request{reqs[r].msg, reqs[r].msg ? reqs[r].len : 0, reqs[r].lo, reqs[r].hi};
+    call_deadline(ctx, whole.data(), n, t0);
+    for (Device& dv : ctx->devs) dv.evnext = 0;
+    return HM_OK;
+}
+// The part of a batch call's stats record every family has.
+template <typename Stats>
+void batch_close(const hm_ctx* ctx, int n, std::chrono::steady_clock::time_point t0, Stats* st) {
+    st->requests = n;
+    st->ndev = (int)ctx->devs.size();
+    st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
+                      .count();
+}
+// A batch call that fails with rc leaves nothing queued: unless rc is a
+// timeout, every stream the devices have made is waited for, then
+// drain_failed (stream 0 and the events).  Returns rc.
+int drain_streams(hm_ctx* ctx, int rc);
 
 // ---- scan.cpp, find.cpp, collect.cpp, verify.cpp: the entry points' bodies, ctx->mu held ----
 int scan_many_locked(hm_ctx* ctx, const hm_request* reqs, int n, hm_result* outs);
@@ -574,8 +689,23 @@ int list_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, const uint64_t* non
                 const hm_result* recs, size_t n, uint64_t target, size_t cap,
                 std::vector<uint64_t>* out, uint64_t* bad);
 // Make *buf hold `want` units of `unit` bytes of device memory (*have: what it
-// holds now); a larger one replaces it and the old one is retired (verify.cpp).
-int grow_buffer(Device& dv, uint64_t** buf, size_t* have, size_t want, size_t most, size_t unit);
+// holds now).  A larger one replaces it -- at least twice the old size, at most
+// `most` units -- and the old one is kept until hm_close, as collect.cpp's
+// record buffer.
+template <typename T>
+int grow_buffer(Device& dv, T** buf, size_t* have, size_t want, size_t most, size_t unit) {
+    if (want <= *have) return HM_OK;
+    const size_t size = std::min(std::max(want, 2 * *have), std::max(most, want));
+    T* b = nullptr;
+    if (hipMalloc(&b, size * unit) != hipSuccess) {
+        (void)hipGetLastError();
+        return HM_ERR_NOMEM;
+    }
+    if (*buf) dv.retired.push_back(*buf);
+    *buf = b;
+    *have = size;
+    return HM_OK;
+}
 // hm_verify_many: per[i] for i < nreq, *refs (the bad (request, index) pairs,
 // ascending, when *bad <= cap; empty otherwise) and *bad.
 int verify_many_locked(hm_ctx* ctx, const hm_verify_request* reqs, int nreq, size_t cap,

@@ -42,23 +42,6 @@ struct ListDev {
 
 }  // namespace
 
-// Make *buf hold `want` units of `unit` bytes (*have: what it holds now).  A
-// larger one replaces it -- at least twice the old size, at most `most` units
-// -- and the old one is kept until hm_close, as collect.cpp's record buffer.
-int grow_buffer(Device& dv, uint64_t** buf, size_t* have, size_t want, size_t most, size_t unit) {
-    if (want <= *have) return HM_OK;
-    const size_t size = std::min(std::max(want, 2 * *have), std::max(most, want));
-    uint64_t* b = nullptr;
-    if (hipMalloc(&b, size * unit) != hipSuccess) {
-        (void)hipGetLastError();
-        return HM_ERR_NOMEM;
-    }
-    if (*buf) dv.retired.push_back(*buf);
-    *buf = b;
-    *have = size;
-    return HM_OK;
-}
-
 int list_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, const uint64_t* nonces,
                 const hm_result* recs, size_t n, uint64_t target, size_t cap,
                 std::vector<uint64_t>* out, uint64_t* bad) {

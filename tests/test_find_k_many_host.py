@@ -73,6 +73,18 @@ def test_makefile_lists_the_new_sources():
         assert f"distributed_bitcoinminer_amd/csrc/{f}" in files, f
 
 
+def test_makefile_lists_the_shared_batch_sources():
+    """The task walker and the chunk runner the three batch calls share."""
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    assert "batch.o" in mk.split("HIP_HOST_OBJS :=")[1].splitlines()[0].rstrip(")").split()
+    deps = mk.split("SRCS_DEPS :=")[1].splitlines()[0].split()
+    assert "fused_tasks.hpp" in deps
+    files = bid.source_files()
+    for f in ("fused_tasks.hpp", "batch.cpp"):
+        assert os.path.exists(os.path.join(CSRC, f)), f
+        assert f"distributed_bitcoinminer_amd/csrc/{f}" in files, f
+
+
 def test_code_object_holds_the_kernel():
     lib = _lib.load()
     p = ctypes.c_void_p()
