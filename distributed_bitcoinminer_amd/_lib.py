@@ -63,7 +63,17 @@ class hm_request(ctypes.Structure):
                 ("lo", ctypes.c_uint64), ("hi", ctypes.c_uint64)]
 
 
-class hm_stats(ctypes.Structure):
+class _Stats(ctypes.Structure):
+    """Base of the stats structs of include/hipminer.h."""
+
+    def as_dict(self) -> dict:
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        if "dom_kernel" in d:
+            d["dom_kernel"] = d["dom_kernel"].decode()
+        return d
+
+
+class hm_stats(_Stats):
     _fields_ = [("wall_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
                 ("dom_kernel_ms", ctypes.c_double), ("nonces", ctypes.c_uint64),
                 ("dom_nonces", ctypes.c_uint64), ("dom_compressions", ctypes.c_uint64),
@@ -74,22 +84,14 @@ class hm_stats(ctypes.Structure):
                 ("enqueue_ms", ctypes.c_double), ("mid_call_syncs", ctypes.c_int32),
                 ("table_grows", ctypes.c_int32), ("deadline_ms", ctypes.c_double)]
 
-    def as_dict(self) -> dict:
-        d = {k: getattr(self, k) for k, _ in self._fields_}
-        d["dom_kernel"] = self.dom_kernel.decode()
-        return d
 
-
-class hm_find_stats(ctypes.Structure):
+class hm_find_stats(_Stats):
     """hm_find_stats of include/hipminer.h (ABI 1.10)."""
     _fields_ = [("wall_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
                 ("nonces_enqueued", ctypes.c_uint64), ("tasks_total", ctypes.c_uint64),
                 ("tasks_run", ctypes.c_uint64), ("launches", ctypes.c_int32),
                 ("ndev", ctypes.c_int32), ("found", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)]
-
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
 class hm_find_request(ctypes.Structure):
@@ -99,7 +101,7 @@ class hm_find_request(ctypes.Structure):
                 ("target", ctypes.c_uint64)]
 
 
-class hm_find_many_stats(ctypes.Structure):
+class hm_find_many_stats(_Stats):
     """hm_find_many_stats of include/hipminer.h (ABI 1.13)."""
     _fields_ = [("wall_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
                 ("nonces_enqueued", ctypes.c_uint64), ("tasks_total", ctypes.c_uint64),
@@ -108,20 +110,14 @@ class hm_find_many_stats(ctypes.Structure):
                 ("fallback", ctypes.c_int32), ("launches", ctypes.c_int32),
                 ("ndev", ctypes.c_int32)]
 
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class hm_find_k_stats(ctypes.Structure):
+class hm_find_k_stats(_Stats):
     """hm_find_k_stats of include/hipminer.h (ABI 1.16)."""
     _fields_ = [("wall_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
                 ("nonces_enqueued", ctypes.c_uint64), ("tasks_total", ctypes.c_uint64),
                 ("tasks_run", ctypes.c_uint64), ("records", ctypes.c_uint64),
                 ("launches", ctypes.c_int32), ("ndev", ctypes.c_int32),
                 ("found", ctypes.c_int32), ("fallback", ctypes.c_int32)]
-
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class hm_find_k_request(ctypes.Structure):
@@ -131,7 +127,7 @@ class hm_find_k_request(ctypes.Structure):
                 ("target", ctypes.c_uint64), ("k", ctypes.c_size_t)]
 
 
-class hm_find_k_many_stats(ctypes.Structure):
+class hm_find_k_many_stats(_Stats):
     """hm_find_k_many_stats of include/hipminer.h (ABI 1.17)."""
     _fields_ = [("wall_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
                 ("nonces_enqueued", ctypes.c_uint64), ("tasks_total", ctypes.c_uint64),
@@ -141,31 +137,22 @@ class hm_find_k_many_stats(ctypes.Structure):
                 ("overflow", ctypes.c_int32), ("launches", ctypes.c_int32),
                 ("ndev", ctypes.c_int32)]
 
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class hm_collect_stats(ctypes.Structure):
+class hm_collect_stats(_Stats):
     """hm_collect_stats of include/hipminer.h (ABI 1.11)."""
     _fields_ = [("wall_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
                 ("nonces", ctypes.c_uint64), ("total", ctypes.c_uint64),
                 ("launches", ctypes.c_int32), ("ndev", ctypes.c_int32),
                 ("overflow", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
-
-class hm_verify_stats(ctypes.Structure):
+class hm_verify_stats(_Stats):
     """hm_verify_stats of include/hipminer.h (ABI 1.12)."""
     _fields_ = [("wall_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
                 ("copy_ms", ctypes.c_double), ("records", ctypes.c_uint64),
                 ("bad", ctypes.c_uint64), ("launches", ctypes.c_int32),
                 ("ndev", ctypes.c_int32), ("overflow", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)]
-
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
 class hm_verify_request(ctypes.Structure):
@@ -180,7 +167,7 @@ class hm_bad_ref(ctypes.Structure):
     _fields_ = [("request", ctypes.c_uint64), ("index", ctypes.c_uint64)]
 
 
-class hm_verify_many_stats(ctypes.Structure):
+class hm_verify_many_stats(_Stats):
     """hm_verify_many_stats of include/hipminer.h (ABI 1.14)."""
     _fields_ = [("wall_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
                 ("copy_ms", ctypes.c_double), ("records", ctypes.c_uint64),
@@ -188,9 +175,6 @@ class hm_verify_many_stats(ctypes.Structure):
                 ("requests", ctypes.c_int32), ("launches", ctypes.c_int32),
                 ("copies", ctypes.c_int32), ("ndev", ctypes.c_int32),
                 ("overflow", ctypes.c_int32), ("reserved", ctypes.c_int32)]
-
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
 class hm_collect_request(ctypes.Structure):
@@ -200,7 +184,7 @@ class hm_collect_request(ctypes.Structure):
                 ("target", ctypes.c_uint64)]
 
 
-class hm_collect_many_stats(ctypes.Structure):
+class hm_collect_many_stats(_Stats):
     """hm_collect_many_stats of include/hipminer.h (ABI 1.15)."""
     _fields_ = [("wall_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
                 ("nonces", ctypes.c_uint64), ("total", ctypes.c_uint64),
@@ -209,13 +193,67 @@ class hm_collect_many_stats(ctypes.Structure):
                 ("launches", ctypes.c_int32), ("ndev", ctypes.c_int32),
                 ("overflow", ctypes.c_int32)]
 
-    def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_}
-
 
 HM_COLLECT_CAP_MAX = 1 << 24
 HM_FIND_K_MAX = 1 << 20
 HM_VERIFY_CAP_MAX = 1 << 20
+
+
+def _prototypes() -> dict:
+    """name -> (restype, argtypes) of every function include/hipminer.h
+    declares and of the debug exports this binding uses."""
+    P = ctypes.POINTER
+    i, i64, u64, sz, dbl = (ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_size_t,
+                            ctypes.c_double)
+    ctx, msg, ip, szp, u64p, res = (ctypes.c_void_p, ctypes.c_char_p, P(i), P(sz), P(u64),
+                                    P(hm_result))
+    rng = [msg, sz, u64, u64]  # msg, len, lo, hi
+    table = {
+        "hm_hash": (u64, [msg, sz, u64]),
+        "hm_version": (i, []),
+        "hm_build_id": (ctypes.c_char_p, []),
+        "hm_strerror": (ctypes.c_char_p, [i]),
+        "hm_partition": (i, rng + [i, u64p]),
+        "hm_open": (i, [ip, i, P(ctx)]),
+        "hm_close": (None, [ctx]),
+        "hm_set_option": (i, [ctx, i, i64]),
+        "hm_scan": (i, [ctx] + rng + [res]),
+        "hm_scan_many": (i, [ctx, P(hm_request), i, res]),
+        "hm_scan_checked": (i, [ctx] + rng + [res, u64p, u64p]),
+        "hm_scan_cpu": (i, rng + [i, res]),
+        "hm_scan_stats": (i, [ctx, P(hm_stats)]),
+        "hm_find": (i, [ctx] + rng + [u64, res, ip]),
+        "hm_find_cpu": (i, rng + [u64, i, res, ip]),
+        "hm_find_many": (i, [ctx, P(hm_find_request), i, res, ip]),
+        "hm_find_many_cpu": (i, [P(hm_find_request), i, i, res, ip]),
+        "hm_find_k": (i, [ctx] + rng + [u64, sz, res, szp]),
+        "hm_find_k_cpu": (i, rng + [u64, sz, i, res, szp]),
+        "hm_find_k_many": (i, [ctx, P(hm_find_k_request), i, res, szp]),
+        "hm_find_k_many_cpu": (i, [P(hm_find_k_request), i, i, res, szp]),
+        "hm_collect": (i, [ctx] + rng + [u64, res, sz, u64p]),
+        "hm_collect_cpu": (i, rng + [u64, i, res, sz, u64p]),
+        "hm_collect_many": (i, [ctx, P(hm_collect_request), i, u64p, res, sz, u64p]),
+        "hm_collect_many_cpu": (i, [P(hm_collect_request), i, i, u64p, res, sz, u64p]),
+        "hm_hash_many": (i, [ctx, msg, sz, u64p, sz, u64p]),
+        "hm_hash_many_cpu": (i, [msg, sz, u64p, sz, i, u64p]),
+        "hm_verify": (i, [ctx, msg, sz, res, sz, u64, u64p, sz, u64p]),
+        "hm_verify_cpu": (i, [msg, sz, res, sz, u64, i, u64p, sz, u64p]),
+        "hm_verify_many": (i, [ctx, P(hm_verify_request), i, u64p, P(hm_bad_ref), sz, u64p]),
+        "hm_verify_many_cpu": (i, [P(hm_verify_request), i, i, u64p, P(hm_bad_ref), sz, u64p]),
+        "hm_debug_code_object": (sz, [P(ctypes.c_void_p)]),
+        "hm_debug_auto_deadline_ms": (dbl, rng + [i]),
+        "hm_debug_streams_made": (i, [ctx, i]),
+        "hm_debug_plan": (i, rng + [i, P(i64), i]),
+    }
+    for cls in (hm_stats, hm_find_stats, hm_find_many_stats, hm_find_k_stats,
+                hm_find_k_many_stats, hm_collect_stats, hm_collect_many_stats, hm_verify_stats,
+                hm_verify_many_stats):
+        family = "scan" if cls is hm_stats else cls.__name__[3:-6]
+        table[f"hm_{family}_stats_sized"] = (i, [ctx, P(cls), sz])
+    return table
+
+
+PROTOTYPES = _prototypes()
 
 _lib = None
 _lock = threading.Lock()
@@ -235,152 +273,9 @@ def load() -> ctypes.CDLL:
             raise HipMinerError(HM_ERR_NO_DEVICE,
                                 f"{LIB_PATH} missing: run __graft_entry__.build()")
         lib = ctypes.CDLL(LIB_PATH)
-        u8p = ctypes.c_char_p
-        lib.hm_hash.restype = ctypes.c_uint64
-        lib.hm_hash.argtypes = [u8p, ctypes.c_size_t, ctypes.c_uint64]
-        lib.hm_open.restype = ctypes.c_int
-        lib.hm_open.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int,
-                                ctypes.POINTER(ctypes.c_void_p)]
-        lib.hm_scan.restype = ctypes.c_int
-        lib.hm_scan.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint64,
-                                ctypes.c_uint64, ctypes.POINTER(hm_result)]
-        lib.hm_scan_many.restype = ctypes.c_int
-        lib.hm_scan_many.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_request), ctypes.c_int,
-                                     ctypes.POINTER(hm_result)]
-        lib.hm_scan_checked.restype = ctypes.c_int
-        lib.hm_scan_checked.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint64,
-                                        ctypes.c_uint64, ctypes.POINTER(hm_result),
-                                        ctypes.POINTER(ctypes.c_uint64),
-                                        ctypes.POINTER(ctypes.c_uint64)]
-        lib.hm_scan_stats.restype = ctypes.c_int
-        lib.hm_scan_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_stats)]
-        lib.hm_scan_stats_sized.restype = ctypes.c_int
-        lib.hm_scan_stats_sized.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_stats),
-                                            ctypes.c_size_t]
-        lib.hm_debug_code_object.restype = ctypes.c_size_t
-        lib.hm_debug_code_object.argtypes = [ctypes.POINTER(ctypes.c_void_p)]
-        lib.hm_set_option.restype = ctypes.c_int
-        lib.hm_set_option.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]
-        lib.hm_strerror.restype = ctypes.c_char_p
-        lib.hm_strerror.argtypes = [ctypes.c_int]
-        lib.hm_close.restype = None
-        lib.hm_close.argtypes = [ctypes.c_void_p]
-        lib.hm_version.restype = ctypes.c_int
-        lib.hm_version.argtypes = []
-        lib.hm_build_id.restype = ctypes.c_char_p
-        lib.hm_build_id.argtypes = []
-        lib.hm_partition.restype = ctypes.c_int
-        lib.hm_partition.argtypes = [u8p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64,
-                                     ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
-        lib.hm_scan_cpu.restype = ctypes.c_int
-        lib.hm_scan_cpu.argtypes = [u8p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64,
-                                    ctypes.c_int, ctypes.POINTER(hm_result)]
-        lib.hm_find.restype = ctypes.c_int
-        lib.hm_find.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint64,
-                                ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(hm_result),
-                                ctypes.POINTER(ctypes.c_int)]
-        lib.hm_find_cpu.restype = ctypes.c_int
-        lib.hm_find_cpu.argtypes = [u8p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64,
-                                    ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(hm_result),
-                                    ctypes.POINTER(ctypes.c_int)]
-        lib.hm_find_stats_sized.restype = ctypes.c_int
-        lib.hm_find_stats_sized.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_find_stats),
-                                            ctypes.c_size_t]
-        lib.hm_find_many.restype = ctypes.c_int
-        lib.hm_find_many.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_find_request),
-                                     ctypes.c_int, ctypes.POINTER(hm_result),
-                                     ctypes.POINTER(ctypes.c_int)]
-        lib.hm_find_many_cpu.restype = ctypes.c_int
-        lib.hm_find_many_cpu.argtypes = [ctypes.POINTER(hm_find_request), ctypes.c_int,
-                                         ctypes.c_int, ctypes.POINTER(hm_result),
-                                         ctypes.POINTER(ctypes.c_int)]
-        lib.hm_find_many_stats_sized.restype = ctypes.c_int
-        lib.hm_find_many_stats_sized.argtypes = [ctypes.c_void_p,
-                                                 ctypes.POINTER(hm_find_many_stats),
-                                                 ctypes.c_size_t]
-        lib.hm_find_k.restype = ctypes.c_int
-        lib.hm_find_k.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint64,
-                                  ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t,
-                                  ctypes.POINTER(hm_result), ctypes.POINTER(ctypes.c_size_t)]
-        lib.hm_find_k_cpu.restype = ctypes.c_int
-        lib.hm_find_k_cpu.argtypes = [u8p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64,
-                                      ctypes.c_uint64, ctypes.c_size_t, ctypes.c_int,
-                                      ctypes.POINTER(hm_result), ctypes.POINTER(ctypes.c_size_t)]
-        lib.hm_find_k_stats_sized.restype = ctypes.c_int
-        lib.hm_find_k_stats_sized.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_find_k_stats),
-                                              ctypes.c_size_t]
-        lib.hm_find_k_many.restype = ctypes.c_int
-        lib.hm_find_k_many.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_find_k_request),
-                                       ctypes.c_int, ctypes.POINTER(hm_result),
-                                       ctypes.POINTER(ctypes.c_size_t)]
-        lib.hm_find_k_many_cpu.restype = ctypes.c_int
-        lib.hm_find_k_many_cpu.argtypes = [ctypes.POINTER(hm_find_k_request), ctypes.c_int,
-                                           ctypes.c_int, ctypes.POINTER(hm_result),
-                                           ctypes.POINTER(ctypes.c_size_t)]
-        lib.hm_find_k_many_stats_sized.restype = ctypes.c_int
-        lib.hm_find_k_many_stats_sized.argtypes = [ctypes.c_void_p,
-                                                   ctypes.POINTER(hm_find_k_many_stats),
-                                                   ctypes.c_size_t]
-        lib.hm_collect.restype = ctypes.c_int
-        lib.hm_collect.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_uint64,
-                                   ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(hm_result),
-                                   ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)]
-        lib.hm_collect_cpu.restype = ctypes.c_int
-        lib.hm_collect_cpu.argtypes = [u8p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64,
-                                       ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(hm_result),
-                                       ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)]
-        lib.hm_collect_stats_sized.restype = ctypes.c_int
-        lib.hm_collect_stats_sized.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_collect_stats),
-                                               ctypes.c_size_t]
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        lib.hm_hash_many.restype = ctypes.c_int
-        lib.hm_hash_many.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, u64p, ctypes.c_size_t,
-                                     u64p]
-        lib.hm_hash_many_cpu.restype = ctypes.c_int
-        lib.hm_hash_many_cpu.argtypes = [u8p, ctypes.c_size_t, u64p, ctypes.c_size_t, ctypes.c_int,
-                                         u64p]
-        lib.hm_verify.restype = ctypes.c_int
-        lib.hm_verify.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.POINTER(hm_result),
-                                  ctypes.c_size_t, ctypes.c_uint64, u64p, ctypes.c_size_t, u64p]
-        lib.hm_verify_cpu.restype = ctypes.c_int
-        lib.hm_verify_cpu.argtypes = [u8p, ctypes.c_size_t, ctypes.POINTER(hm_result),
-                                      ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int, u64p,
-                                      ctypes.c_size_t, u64p]
-        lib.hm_verify_stats_sized.restype = ctypes.c_int
-        lib.hm_verify_stats_sized.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_verify_stats),
-                                              ctypes.c_size_t]
-        lib.hm_verify_many.restype = ctypes.c_int
-        lib.hm_verify_many.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_verify_request),
-                                       ctypes.c_int, u64p, ctypes.POINTER(hm_bad_ref),
-                                       ctypes.c_size_t, u64p]
-        lib.hm_verify_many_cpu.restype = ctypes.c_int
-        lib.hm_verify_many_cpu.argtypes = [ctypes.POINTER(hm_verify_request), ctypes.c_int,
-                                           ctypes.c_int, u64p, ctypes.POINTER(hm_bad_ref),
-                                           ctypes.c_size_t, u64p]
-        lib.hm_verify_many_stats_sized.restype = ctypes.c_int
-        lib.hm_verify_many_stats_sized.argtypes = [ctypes.c_void_p,
-                                                   ctypes.POINTER(hm_verify_many_stats),
-                                                   ctypes.c_size_t]
-        lib.hm_collect_many.restype = ctypes.c_int
-        lib.hm_collect_many.argtypes = [ctypes.c_void_p, ctypes.POINTER(hm_collect_request),
-                                        ctypes.c_int, u64p, ctypes.POINTER(hm_result),
-                                        ctypes.c_size_t, u64p]
-        lib.hm_collect_many_cpu.restype = ctypes.c_int
-        lib.hm_collect_many_cpu.argtypes = [ctypes.POINTER(hm_collect_request), ctypes.c_int,
-                                            ctypes.c_int, u64p, ctypes.POINTER(hm_result),
-                                            ctypes.c_size_t, u64p]
-        lib.hm_collect_many_stats_sized.restype = ctypes.c_int
-        lib.hm_collect_many_stats_sized.argtypes = [ctypes.c_void_p,
-                                                    ctypes.POINTER(hm_collect_many_stats),
-                                                    ctypes.c_size_t]
-        lib.hm_debug_auto_deadline_ms.restype = ctypes.c_double
-        lib.hm_debug_auto_deadline_ms.argtypes = [u8p, ctypes.c_size_t, ctypes.c_uint64,
-                                                  ctypes.c_uint64, ctypes.c_int]
-        lib.hm_debug_streams_made.restype = ctypes.c_int
-        lib.hm_debug_streams_made.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        lib.hm_debug_plan.restype = ctypes.c_int
-        lib.hm_debug_plan.argtypes = [u8p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64,
-                                      ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int]
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
         return lib
 
@@ -450,12 +345,16 @@ class Context:
             raise HipMinerError(rc, "hm_scan_many")
         return [(int(outs[i].hash), int(outs[i].nonce)) for i in range(n)]
 
-    def stats(self) -> dict:
-        st = hm_stats()
-        rc = self._lib.hm_scan_stats_sized(self._h, ctypes.byref(st), ctypes.sizeof(st))
+    def _stats(self, getter: str, cls, what: str = None) -> dict:
+        """The family's stats record through its hm_X_stats_sized, as a dict."""
+        st = cls()
+        rc = getattr(self._lib, getter)(self._h, ctypes.byref(st), ctypes.sizeof(st))
         if rc != HM_OK:
-            raise HipMinerError(rc, "hm_scan_stats")
+            raise HipMinerError(rc, what or getter)
         return st.as_dict()
+
+    def stats(self) -> dict:
+        return self._stats("hm_scan_stats_sized", hm_stats, "hm_scan_stats")
 
     def find(self, msg, lo: int, hi: int, target: int):
         """hm_find (ABI 1.10): (hash, nonce) of the LOWEST nonce in the
@@ -472,11 +371,7 @@ class Context:
 
     def find_stats(self) -> dict:
         """hm_find_stats_sized: work accounting of the last find on this context."""
-        st = hm_find_stats()
-        rc = self._lib.hm_find_stats_sized(self._h, ctypes.byref(st), ctypes.sizeof(st))
-        if rc != HM_OK:
-            raise HipMinerError(rc, "hm_find_stats_sized")
-        return st.as_dict()
+        return self._stats("hm_find_stats_sized", hm_find_stats)
 
     def find_many(self, requests):
         """hm_find_many (ABI 1.13) over [(msg, lo, hi, target), ...]: for each
@@ -487,11 +382,7 @@ class Context:
 
     def find_many_stats(self) -> dict:
         """hm_find_many_stats_sized: work accounting of the last find_many on this context."""
-        st = hm_find_many_stats()
-        rc = self._lib.hm_find_many_stats_sized(self._h, ctypes.byref(st), ctypes.sizeof(st))
-        if rc != HM_OK:
-            raise HipMinerError(rc, "hm_find_many_stats_sized")
-        return st.as_dict()
+        return self._stats("hm_find_many_stats_sized", hm_find_many_stats)
 
     def find_k(self, msg, lo: int, hi: int, target: int, k: int):
         """hm_find_k (ABI 1.16): the (hash, nonce) of the k LOWEST nonces in the
@@ -503,11 +394,7 @@ class Context:
 
     def find_k_stats(self) -> dict:
         """hm_find_k_stats_sized: work accounting of the last find_k on this context."""
-        st = hm_find_k_stats()
-        rc = self._lib.hm_find_k_stats_sized(self._h, ctypes.byref(st), ctypes.sizeof(st))
-        if rc != HM_OK:
-            raise HipMinerError(rc, "hm_find_k_stats_sized")
-        return st.as_dict()
+        return self._stats("hm_find_k_stats_sized", hm_find_k_stats)
 
     def find_k_many(self, requests):
         """hm_find_k_many (ABI 1.17) over [(msg, lo, hi, target, k), ...]: for
@@ -519,11 +406,7 @@ class Context:
 
     def find_k_many_stats(self) -> dict:
         """hm_find_k_many_stats_sized: work accounting of the last find_k_many."""
-        st = hm_find_k_many_stats()
-        rc = self._lib.hm_find_k_many_stats_sized(self._h, ctypes.byref(st), ctypes.sizeof(st))
-        if rc != HM_OK:
-            raise HipMinerError(rc, "hm_find_k_many_stats_sized")
-        return st.as_dict()
+        return self._stats("hm_find_k_many_stats_sized", hm_find_k_many_stats)
 
     def collect(self, msg, lo: int, hi: int, target: int, cap: int):
         """hm_collect (ABI 1.11): (total, records).  total = the number of
@@ -539,11 +422,7 @@ class Context:
 
     def collect_stats(self) -> dict:
         """hm_collect_stats_sized: work accounting of the last collect on this context."""
-        st = hm_collect_stats()
-        rc = self._lib.hm_collect_stats_sized(self._h, ctypes.byref(st), ctypes.sizeof(st))
-        if rc != HM_OK:
-            raise HipMinerError(rc, "hm_collect_stats_sized")
-        return st.as_dict()
+        return self._stats("hm_collect_stats_sized", hm_collect_stats)
 
     def collect_many(self, requests, cap: int):
         """hm_collect_many (ABI 1.15) over [(msg, lo, hi, target), ...]:
@@ -562,11 +441,7 @@ class Context:
 
     def collect_many_stats(self) -> dict:
         """hm_collect_many_stats_sized: work accounting of the last collect_many."""
-        st = hm_collect_many_stats()
-        rc = self._lib.hm_collect_many_stats_sized(self._h, ctypes.byref(st), ctypes.sizeof(st))
-        if rc != HM_OK:
-            raise HipMinerError(rc, "hm_collect_many_stats_sized")
-        return st.as_dict()
+        return self._stats("hm_collect_many_stats_sized", hm_collect_many_stats)
 
     def hash_many(self, msg, nonces):
         """hm_hash_many (ABI 1.12): numpy.uint64 array of Hash(msg, n) for each
@@ -586,11 +461,7 @@ class Context:
 
     def verify_stats(self) -> dict:
         """hm_verify_stats_sized: accounting of the last hash_many or verify."""
-        st = hm_verify_stats()
-        rc = self._lib.hm_verify_stats_sized(self._h, ctypes.byref(st), ctypes.sizeof(st))
-        if rc != HM_OK:
-            raise HipMinerError(rc, "hm_verify_stats_sized")
-        return st.as_dict()
+        return self._stats("hm_verify_stats_sized", hm_verify_stats)
 
     def verify_many(self, requests, cap: int):
         """hm_verify_many (ABI 1.14) over [(msg, records, target), ...]:
@@ -603,11 +474,7 @@ class Context:
 
     def verify_many_stats(self) -> dict:
         """hm_verify_many_stats_sized: accounting of the last verify_many."""
-        st = hm_verify_many_stats()
-        rc = self._lib.hm_verify_many_stats_sized(self._h, ctypes.byref(st), ctypes.sizeof(st))
-        if rc != HM_OK:
-            raise HipMinerError(rc, "hm_verify_many_stats_sized")
-        return st.as_dict()
+        return self._stats("hm_verify_many_stats_sized", hm_verify_many_stats)
 
     def streams_made(self, device_index: int = 0) -> int:
         """HIP streams (hardware queues) the context has made on its
@@ -667,18 +534,30 @@ def find_cpu(msg, lo: int, hi: int, target: int, threads: int = 0):
     return (int(out.hash), int(out.nonce)) if found.value else None
 
 
+def _requests(cls, requests):
+    """[(msg, ...), ...] as an array of the request struct cls, whose fields are
+    msg, len and then the tuple's other members: (array, n, the byte strings
+    the array borrows -- keep them alive for the call).  A msg of None becomes
+    a NULL pointer with len 0."""
+    reqs = list(requests)
+    n = len(reqs)
+    keep = [None if r[0] is None else as_bytes(r[0]) for r in reqs]
+    arr = (cls * max(1, n))()
+    for i, (r, m) in enumerate(zip(reqs, keep)):
+        if len(r) + 1 != len(cls._fields_):
+            raise ValueError(f"{cls.__name__}: {len(cls._fields_) - 1} values expected, got {r!r}")
+        arr[i] = cls(m, len(m) if m is not None else 0, *r[1:])
+    return arr, n, keep
+
+
 def _find_many(call, what: str, requests):
     """Run a find_many entry point over [(msg, lo, hi, target), ...] and shape
     its answers: a list of (hash, nonce) or None."""
-    reqs = list(requests)
-    n = len(reqs)
-    keep = [as_bytes(r[0]) for r in reqs]
-    arr = (hm_find_request * max(1, n))()
-    for i, ((_, lo, hi, target), m) in enumerate(zip(reqs, keep)):
-        arr[i] = hm_find_request(m, len(m), lo, hi, target)
+    arr, n, keep = _requests(hm_find_request, requests)
     outs = (hm_result * max(1, n))()
     found = (ctypes.c_int * max(1, n))()
     rc = call(arr, n, outs, found)
+    del keep
     if rc != HM_OK:
         raise HipMinerError(rc, what)
     return [(int(outs[i].hash), int(outs[i].nonce)) if found[i] else None for i in range(n)]
@@ -713,16 +592,8 @@ def find_k_cpu(msg, lo: int, hi: int, target: int, k: int, threads: int = 0):
 
 
 def find_k_requests(requests):
-    """[(msg, lo, hi, target, k), ...] as an hm_find_k_request array: (array,
-    n, the byte strings the array borrows -- keep them alive for the call).  A
-    msg of None becomes a NULL pointer with len 0."""
-    reqs = list(requests)
-    n = len(reqs)
-    keep = [None if r[0] is None else as_bytes(r[0]) for r in reqs]
-    arr = (hm_find_k_request * max(1, n))()
-    for i, ((_, lo, hi, target, k), m) in enumerate(zip(reqs, keep)):
-        arr[i] = hm_find_k_request(m, len(m) if m is not None else 0, lo, hi, target, k)
-    return arr, n, keep
+    """[(msg, lo, hi, target, k), ...] as an hm_find_k_request array (_requests)."""
+    return _requests(hm_find_k_request, requests)
 
 
 def _find_k_many(call, what: str, requests):
@@ -782,16 +653,8 @@ def count_cpu(msg, lo: int, hi: int, target: int, threads: int = 0) -> int:
 
 
 def collect_requests(requests):
-    """[(msg, lo, hi, target), ...] as an hm_collect_request array: (array, n,
-    the byte strings the array borrows -- keep them alive for the call).  A
-    msg of None becomes a NULL pointer with len 0."""
-    reqs = list(requests)
-    n = len(reqs)
-    keep = [None if r[0] is None else as_bytes(r[0]) for r in reqs]
-    arr = (hm_collect_request * max(1, n))()
-    for i, ((_, lo, hi, target), m) in enumerate(zip(reqs, keep)):
-        arr[i] = hm_collect_request(m, len(m) if m is not None else 0, lo, hi, target)
-    return arr, n, keep
+    """[(msg, lo, hi, target), ...] as an hm_collect_request array (_requests)."""
+    return _requests(hm_collect_request, requests)
 
 
 def _collect_many(call, what: str, requests, cap: int):

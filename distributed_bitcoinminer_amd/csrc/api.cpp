@@ -32,7 +32,10 @@
 //   fused_find_k_kernels.hip per request, hm_find_k's path for what is left.
 //   The three *_many calls above share one chunk runner on the host
 //   (batch.cpp); fused_tasks.hpp has the fused batch kernels' task walker
-//   (hm_fused_find_kernel runs on it).
+//   (hm_fused_find_kernel runs on it).  hm_find and hm_find_k share one
+//   early-exit walk (find_walk), every family's stats getter is stats_out over
+//   its StatsSlot of hm_ctx (both hm_internal.hpp), and guarded() and the
+//   null-message rule (msg_or_empty) are plan.hpp's, shared with host_scan.cpp.
 //   The scan kernels come from their own code object (scan_kernels.hip ->
 //   align_loops.py -> hipminer_scan.hsaco, embedded by scan_blob.S), loaded
 //   per device with hipModuleLoadData and launched with hipModuleLaunchKernel.
@@ -48,8 +51,8 @@ extern "C" const unsigned char hm_scan_code_object_end[];
 extern "C" {
 
 uint64_t hm_hash(const uint8_t* msg, size_t len, uint64_t nonce) {
-    static const uint8_t empty = 0;
-    return host_hash(msg ? msg : &empty, msg ? len : 0, nonce);
+    const Msg m = msg_or_empty(msg, len);
+    return host_hash(m.p, m.len, nonce);
 }
 
 // 1.1: hm_scan_many, hm_stats.dom_*; 1.2: hm_partition; 1.3: hm_scan_checked;
@@ -81,8 +84,7 @@ int hm_partition(const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, int n
                  uint64_t* bounds) {
     if (n <= 0 || !bounds || (len > 0 && !msg)) return HM_ERR_INVALID;
     return guarded([&] {
-        static const uint8_t empty = 0;
-        const MsgPlan mp = plan_message(msg ? msg : &empty, msg ? len : 0);
+        const MsgPlan mp = plan_message(msg_or_empty(msg, len));
         const std::vector<Shard> sh = partition_range(mp, lo, hi, n, false);
         for (int i = 0; i < n; ++i) {
             bounds[2 * i] = sh[i].empty ? 1 : sh[i].lo;
@@ -265,11 +267,7 @@ int hm_find(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t h
 }
 
 int hm_find_stats_sized(const hm_ctx* ctx, hm_find_stats* out, size_t size) {
-    if (!ctx || !out || size < HM_FIND_STATS_SIZE_1_10) return HM_ERR_INVALID;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if (!ctx->have_find_stats) return HM_ERR_INVALID;
-    memcpy(out, &ctx->last_find, std::min(size, sizeof(hm_find_stats)));
-    return HM_OK;
+    return stats_out(ctx, &hm_ctx::find_stats, out, size, HM_FIND_STATS_SIZE_1_10);
 }
 
 int hm_find_many(hm_ctx* ctx, const hm_find_request* reqs, int n, hm_result* outs, int* found) {
@@ -294,11 +292,7 @@ int hm_find_many(hm_ctx* ctx, const hm_find_request* reqs, int n, hm_result* out
 }
 
 int hm_find_many_stats_sized(const hm_ctx* ctx, hm_find_many_stats* out, size_t size) {
-    if (!ctx || !out || size < HM_FIND_MANY_STATS_SIZE_1_13) return HM_ERR_INVALID;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if (!ctx->have_find_many_stats) return HM_ERR_INVALID;
-    memcpy(out, &ctx->last_find_many, std::min(size, sizeof(hm_find_many_stats)));
-    return HM_OK;
+    return stats_out(ctx, &hm_ctx::find_many_stats, out, size, HM_FIND_MANY_STATS_SIZE_1_13);
 }
 
 int hm_find_k(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
@@ -315,11 +309,7 @@ int hm_find_k(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t
 }
 
 int hm_find_k_stats_sized(const hm_ctx* ctx, hm_find_k_stats* out, size_t size) {
-    if (!ctx || !out || size < HM_FIND_K_STATS_SIZE_1_16) return HM_ERR_INVALID;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if (!ctx->have_find_k_stats) return HM_ERR_INVALID;
-    memcpy(out, &ctx->last_find_k, std::min(size, sizeof(hm_find_k_stats)));
-    return HM_OK;
+    return stats_out(ctx, &hm_ctx::find_k_stats, out, size, HM_FIND_K_STATS_SIZE_1_16);
 }
 
 int hm_find_k_many(hm_ctx* ctx, const hm_find_k_request* reqs, int n, hm_result* out,
@@ -344,11 +334,7 @@ int hm_find_k_many(hm_ctx* ctx, const hm_find_k_request* reqs, int n, hm_result*
 }
 
 int hm_find_k_many_stats_sized(const hm_ctx* ctx, hm_find_k_many_stats* out, size_t size) {
-    if (!ctx || !out || size < HM_FIND_K_MANY_STATS_SIZE_1_17) return HM_ERR_INVALID;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if (!ctx->have_find_k_many_stats) return HM_ERR_INVALID;
-    memcpy(out, &ctx->last_find_k_many, std::min(size, sizeof(hm_find_k_many_stats)));
-    return HM_OK;
+    return stats_out(ctx, &hm_ctx::find_k_many_stats, out, size, HM_FIND_K_MANY_STATS_SIZE_1_17);
 }
 
 int hm_collect(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
@@ -368,11 +354,7 @@ int hm_collect(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_
 }
 
 int hm_collect_stats_sized(const hm_ctx* ctx, hm_collect_stats* out, size_t size) {
-    if (!ctx || !out || size < HM_COLLECT_STATS_SIZE_1_11) return HM_ERR_INVALID;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if (!ctx->have_collect_stats) return HM_ERR_INVALID;
-    memcpy(out, &ctx->last_collect, std::min(size, sizeof(hm_collect_stats)));
-    return HM_OK;
+    return stats_out(ctx, &hm_ctx::collect_stats, out, size, HM_COLLECT_STATS_SIZE_1_11);
 }
 
 int hm_collect_many(hm_ctx* ctx, const hm_collect_request* reqs, int n, uint64_t* totals,
@@ -396,11 +378,7 @@ int hm_collect_many(hm_ctx* ctx, const hm_collect_request* reqs, int n, uint64_t
 }
 
 int hm_collect_many_stats_sized(const hm_ctx* ctx, hm_collect_many_stats* out, size_t size) {
-    if (!ctx || !out || size < HM_COLLECT_MANY_STATS_SIZE_1_15) return HM_ERR_INVALID;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if (!ctx->have_collect_many_stats) return HM_ERR_INVALID;
-    memcpy(out, &ctx->last_collect_many, std::min(size, sizeof(hm_collect_many_stats)));
-    return HM_OK;
+    return stats_out(ctx, &hm_ctx::collect_many_stats, out, size, HM_COLLECT_MANY_STATS_SIZE_1_15);
 }
 
 int hm_hash_many(hm_ctx* ctx, const uint8_t* msg, size_t len, const uint64_t* nonces, size_t n,
@@ -435,11 +413,7 @@ int hm_verify(hm_ctx* ctx, const uint8_t* msg, size_t len, const hm_result* recs
 }
 
 int hm_verify_stats_sized(const hm_ctx* ctx, hm_verify_stats* out, size_t size) {
-    if (!ctx || !out || size < HM_VERIFY_STATS_SIZE_1_12) return HM_ERR_INVALID;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if (!ctx->have_verify_stats) return HM_ERR_INVALID;
-    memcpy(out, &ctx->last_verify, std::min(size, sizeof(hm_verify_stats)));
-    return HM_OK;
+    return stats_out(ctx, &hm_ctx::verify_stats, out, size, HM_VERIFY_STATS_SIZE_1_12);
 }
 
 int hm_verify_many(hm_ctx* ctx, const hm_verify_request* reqs, int nreq, uint64_t* bad_per_req,
@@ -463,11 +437,7 @@ int hm_verify_many(hm_ctx* ctx, const hm_verify_request* reqs, int nreq, uint64_
 }
 
 int hm_verify_many_stats_sized(const hm_ctx* ctx, hm_verify_many_stats* out, size_t size) {
-    if (!ctx || !out || size < HM_VERIFY_MANY_STATS_SIZE_1_14) return HM_ERR_INVALID;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    if (!ctx->have_verify_many_stats) return HM_ERR_INVALID;
-    memcpy(out, &ctx->last_verify_many, std::min(size, sizeof(hm_verify_many_stats)));
-    return HM_OK;
+    return stats_out(ctx, &hm_ctx::verify_many_stats, out, size, HM_VERIFY_MANY_STATS_SIZE_1_14);
 }
 
 int hm_scan_stats(const hm_ctx* ctx, hm_stats* out) {
@@ -477,13 +447,7 @@ int hm_scan_stats(const hm_ctx* ctx, hm_stats* out) {
 }
 
 int hm_scan_stats_sized(const hm_ctx* ctx, hm_stats* out, size_t size) {
-    // a caller built against an older header passes its smaller struct:
-    // only its prefix is written (the layout only ever grows at the end)
-    if (!ctx || !out || size < HM_STATS_SIZE_1_0) return HM_ERR_INVALID;
-    std::lock_guard<std::mutex> g(ctx->mu);  // scans write ctx->last under the lock
-    if (!ctx->have_stats) return HM_ERR_INVALID;
-    memcpy(out, &ctx->last, std::min(size, sizeof(hm_stats)));
-    return HM_OK;
+    return stats_out(ctx, &hm_ctx::scan_stats, out, size, HM_STATS_SIZE_1_0);
 }
 
 // ---- debug exports for host-side tests (include/hipminer_debug.h) ----
@@ -522,8 +486,7 @@ int hm_debug_streams_made(const hm_ctx* ctx, int i) {
 int hm_debug_plan(const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, int force_generic,
                   int64_t* outv, int cap) {
     if (lo > hi) return 0;
-    static const uint8_t empty = 0;
-    const MsgPlan mp = plan_message(msg ? msg : &empty, msg ? len : 0);
+    const MsgPlan mp = plan_message(msg_or_empty(msg, len));
     std::vector<SegPlan> segs;
     try {
         segs = plan_range(mp, lo, hi, force_generic != 0);

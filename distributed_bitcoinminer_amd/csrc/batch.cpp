@@ -41,12 +41,12 @@ BatchChunk::BatchChunk(hm_ctx* ctx, int index0, uint64_t window, bool whole)
 
 BatchReq& BatchChunk::add(const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
                           uint64_t target) {
-    static const uint8_t empty_msg = 0;
     const uint64_t W = window;
     rq.emplace_back();
     BatchReq& R = rq.back();
-    R.m = msg ? msg : &empty_msg;
-    R.mlen = msg ? len : 0;
+    const Msg e = msg_or_empty(msg, len);
+    R.m = e.p;
+    R.mlen = e.len;
     R.live = lo <= hi && target != 0;
     R.dev = (index0 + (int)rq.size() - 1) % ndev;
     if (!R.live || !ctx->fused || (whole && hi - lo > W - 1)) return R;
@@ -75,8 +75,8 @@ int BatchChunk::prepare(uint64_t* Device::*ctl_buf, size_t words) {
         Device& dv = ctx->devs[i];
         if (!nfused[i]) continue;
         HIPCHK(hipSetDevice(dv.ordinal));
-        if (!(dv.*ctl_buf)) HIPCHK(hipMalloc(&(dv.*ctl_buf), words * sizeof(uint64_t)));
-        int rc = make_streams(dv, used(i));
+        int rc = ctl_block(&(dv.*ctl_buf), words);
+        if (!rc) rc = make_streams(dv, used(i));
         if (rc) return rc;
     }
     return HM_OK;

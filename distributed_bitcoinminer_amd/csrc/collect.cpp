@@ -29,24 +29,6 @@ struct CollectDev {
 
 }  // namespace
 
-// Make dv's record buffer hold `cap` records.  A larger one replaces it (at
-// least twice the old size, so all the buffers a device retires together are
-// smaller than its current one); the old buffer is kept until hm_close, as
-// the K+W tables are (hipFree would wait for the whole device).
-int collect_buffer(Device& dv, size_t cap) {
-    if (cap <= dv.collect_cap) return HM_OK;
-    const size_t want = std::min<size_t>(std::max(cap, 2 * dv.collect_cap), HM_COLLECT_CAP_MAX);
-    uint64_t* b = nullptr;
-    if (hipMalloc(&b, want * sizeof(hm_result)) != hipSuccess) {
-        (void)hipGetLastError();
-        return HM_ERR_NOMEM;
-    }
-    if (dv.collect_buf) dv.retired.push_back(dv.collect_buf);
-    dv.collect_buf = b;
-    dv.collect_cap = want;
-    return HM_OK;
-}
-
 // Slots are handed out in dispatch order, the answer is in nonce order: sort,
 // then every record is distinct, inside [lo, hi] and below the target.
 int sort_check_records(std::vector<hm_result>* recs, uint64_t lo, uint64_t hi, uint64_t target) {
@@ -204,14 +186,10 @@ int collect_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uin
     hm_collect_stats st{};
     st.kernel_ms = tally.kernel_ms;
     st.total = sum;
-    st.ndev = (int)ctx->devs.size();
     st.overflow = sum > cap ? 1 : 0;
     st.nonces = tally.nonces;
     st.launches = tally.launches;
-    st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
-                     .count();
-    ctx->last_collect = st;
-    ctx->have_collect_stats = true;
+    publish(ctx, ctx->collect_stats, st, t0);
     *total = sum;
     return HM_OK;
 }

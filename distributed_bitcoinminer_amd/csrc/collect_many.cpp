@@ -207,9 +207,8 @@ int collect_many_locked(hm_ctx* ctx, const hm_collect_request* reqs, int n, size
     }
     st.total = G.sum;
     st.overflow = G.overflow ? 1 : 0;
-    batch_close(ctx, n, t0, &st);
-    ctx->last_collect_many = st;
-    ctx->have_collect_many_stats = true;
+    st.requests = n;
+    publish(ctx, ctx->collect_many_stats, st, t0);
     *total = G.sum;
     return HM_OK;
 }

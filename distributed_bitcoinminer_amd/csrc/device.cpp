@@ -275,12 +275,11 @@ constexpr double kDeadlineSlack = 8.0;
 
 double modelled_deadline_ms(const hm_request* reqs, int n, bool force_generic, int table_digits,
                             double simds) {
-    static const uint8_t empty_msg = 0;
     long double cycles = 0;
     for (int r = 0; r < n; ++r) {
         const hm_request& q = reqs[r];
         if (q.lo > q.hi) continue;
-        const MsgPlan mp = plan_message(q.msg ? q.msg : &empty_msg, q.msg ? q.len : 0);
+        const MsgPlan mp = plan_message(msg_or_empty(q.msg, q.len));
         for (const SegPlan& g : plan_range(mp, q.lo, q.hi, force_generic, table_digits))
             cycles += ((long double)(g.hi - g.lo) + 1) * seg_cost(g) / kWaveSize;
     }

@@ -30,9 +30,9 @@
 // A hit at nonce MaxUint64 cannot be told from "none" in the stop word, so
 // the kernels never publish it and the host tests that one nonce itself.
 //
-// The walk itself -- FindDev, find_next_step, find_issue (hm_internal.hpp) and
-// find_collect -- is shared with hm_find_k (find_k.cpp), which runs it over
-// its own kernels, trailer and control words.
+// The walk itself -- find_walk over FindDev, find_next_step, find_issue
+// (hm_internal.hpp) and find_collect -- is shared with hm_find_k (find_k.cpp),
+// which runs it over its own kernels, trailer and control words.
 // ---------------------------------------------------------------------------
 #include "hm_internal.hpp"
 
@@ -89,8 +89,6 @@ int find_collect(hm_ctx* ctx, Device& dv, FindDev& fd, FindTally& tally, const u
 
 int find_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_t hi, uint64_t target,
               FindTally* tally_out, hm_result* out, int* found) {
-    int rc;
-    const int ndev = (int)ctx->devs.size();
     FindTally& tally = *tally_out;
     uint64_t best = ~0ull;
     if (lo <= hi && target != 0) {
@@ -104,46 +102,17 @@ int find_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_t 
         }
         // the per-device state dies with the call: a failure only has to
         // drain the streams (drain_failed)
-        std::vector<FindDev> fds(ndev);
-        PieceWalk pieces(ctx, mp, lo, hi);
-        std::vector<std::vector<SegPlan>> shards;
-        // later pieces lie above a hit
-        while (best == ~0ull && pieces.next(&shards)) {
-            for (int i = 0; i < ndev; ++i) {
-                fds[i].segs = std::move(shards[i]);
-                fds[i].si = 0;
-                fds[i].seg_open = false;
-            }
-            for (;;) {
-                bool any = false;
-                for (int i = 0; i < ndev; ++i) {
-                    Device& dv = ctx->devs[i];
-                    HIPCHK(hipSetDevice(dv.ordinal));
-                    while (fds[i].inflight < kFindLookahead) {
-                        bool issued = false;
-                        rc = find_issue(ctx, dv, fds[i], mp, Family::Find, best, tally, &issued,
-                                        [&](uint64_t launch_lo) {
-                                            FindArgs fa;
-                                            fa.word = dv.find_ctl;
-                                            fa.tasks_run = dv.find_ctl + 1;
-                                            fa.target = target;
-                                            fa.launch_lo = launch_lo;
-                                            return fa;
-                                        });
-                        if (rc) return drain_failed(ctx, rc);
-                        if (!issued) break;
-                    }
-                    any = any || fds[i].inflight > 0;
-                }
-                if (!any) break;
-                for (int i = 0; i < ndev; ++i) {
-                    if (!fds[i].inflight) continue;
-                    rc = find_collect(ctx, ctx->devs[i], fds[i], tally, ctx->devs[i].find_ctl, 2);
-                    if (rc) return drain_failed(ctx, rc);
-                    best = std::min(best, fds[i].ctl[0]);
-                }
-            }
-        }
+        std::vector<FindDev> fds(ctx->devs.size());
+        int rc = find_walk(ctx, mp, lo, hi, Family::Find, &Device::find_ctl, 2, fds, tally, &best,
+                           [&](Device& dv, uint64_t launch_lo) {
+                               FindArgs fa;
+                               fa.word = dv.find_ctl;
+                               fa.tasks_run = dv.find_ctl + 1;
+                               fa.target = target;
+                               fa.launch_lo = launch_lo;
+                               return fa;
+                           });
+        if (rc) return rc;
         for (const FindDev& fd : fds) tally.run += fd.ctl[1];
     }
     hm_result res{~0ull, 0};
@@ -181,12 +150,8 @@ int find_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64
     st.tasks_total = tally.tasks;
     st.tasks_run = tally.run;
     st.launches = tally.launches;
-    st.ndev = (int)ctx->devs.size();
     st.found = hit;
-    st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
-                     .count();
-    ctx->last_find = st;
-    ctx->have_find_stats = true;
+    publish(ctx, ctx->find_stats, st, t0);
     *out = res;
     *found = hit;
     return HM_OK;

@@ -3,8 +3,8 @@
 // hm_find_k: the k lowest nonces of [lo, hi] whose hash is below `target`
 // (find_k_kernels.hip has the device protocol and its four invariants).
 //
-// Host side.  hm_find's walk (find.cpp: PieceWalk, FindDev, find_issue,
-// find_collect): pieces in ascending order, within a piece every device walks
+// Host side.  hm_find's walk (find_walk, hm_internal.hpp; find.cpp has its
+// rules): pieces in ascending order, within a piece every device walks
 // its shard's launches in ascending order on stream 0, at most kFindLookahead
 // in flight, and after each batch its control words are read back.  The
 // pruning bound is the minimum of the devices' stop words: a device lowers its
@@ -84,7 +84,8 @@ int find_k_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_
             dv.evnext = 0;
             rc = collect_buffer(dv, B);
             if (rc) return rc;
-            if (!dv.find_k_ctl) HIPCHK(hipMalloc(&dv.find_k_ctl, kFkWords * sizeof(uint64_t)));
+            rc = ctl_block(&dv.find_k_ctl, kFkWords);
+            if (rc) return rc;
             // the stop word starts at MaxUint64, the other four words at 0
             static_assert(kFkStop == 0, "the stop word is the first of the control words");
             HIPCHK(hipMemsetAsync(dv.find_k_ctl, 0xff, sizeof(uint64_t), dv.stream[0]));
@@ -94,49 +95,18 @@ int find_k_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_
         // the per-device state dies with the call: a failure only has to
         // drain the streams (drain_failed)
         std::vector<FindDev> fds(ndev);
-        PieceWalk pieces(ctx, mp, lo, hi);
-        std::vector<std::vector<SegPlan>> shards;
-        // later pieces lie above every record written so far, the bound among them
-        while (best == ~0ull && pieces.next(&shards)) {
-            for (int i = 0; i < ndev; ++i) {
-                fds[i].segs = std::move(shards[i]);
-                fds[i].si = 0;
-                fds[i].seg_open = false;
-            }
-            for (;;) {
-                bool any = false;
-                for (int i = 0; i < ndev; ++i) {
-                    Device& dv = ctx->devs[i];
-                    if (hipSetDevice(dv.ordinal) != hipSuccess)
-                        return drain_failed(ctx, HM_ERR_HIP);
-                    while (fds[i].inflight < kFindLookahead) {
-                        bool issued = false;
-                        rc = find_issue(ctx, dv, fds[i], mp, Family::FindK, best, tally, &issued,
-                                        [&](uint64_t launch_lo) {
-                                            FindKArgs ka;
-                                            ka.ctl = dv.find_k_ctl;
-                                            ka.out = dv.collect_buf;
-                                            ka.target = target;
-                                            ka.launch_lo = launch_lo;
-                                            ka.cap = (uint32_t)B;
-                                            ka.k = (uint32_t)k;
-                                            return ka;
-                                        });
-                        if (rc) return drain_failed(ctx, rc);
-                        if (!issued) break;
-                    }
-                    any = any || fds[i].inflight > 0;
-                }
-                if (!any) break;
-                for (int i = 0; i < ndev; ++i) {
-                    if (!fds[i].inflight) continue;
-                    rc = find_collect(ctx, ctx->devs[i], fds[i], tally, ctx->devs[i].find_k_ctl,
-                                      kFkWords);
-                    if (rc) return drain_failed(ctx, rc);
-                    best = std::min(best, fds[i].ctl[kFkStop]);
-                }
-            }
-        }
+        rc = find_walk(ctx, mp, lo, hi, Family::FindK, &Device::find_k_ctl, kFkWords, fds, tally,
+                       &best, [&](Device& dv, uint64_t launch_lo) {
+                           FindKArgs ka;
+                           ka.ctl = dv.find_k_ctl;
+                           ka.out = dv.collect_buf;
+                           ka.target = target;
+                           ka.launch_lo = launch_lo;
+                           ka.cap = (uint32_t)B;
+                           ka.k = (uint32_t)k;
+                           return ka;
+                       });
+        if (rc) return rc;
         // every stream is idle: the records of every device
         for (int i = 0; i < ndev; ++i) {
             const uint64_t cursor = fds[i].ctl[kFkCursor];
@@ -181,27 +151,20 @@ int find_k_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint
     size_t mlen;
     int rc = begin_ranged_call(ctx, msg, len, lo, hi, t0, &m, &mlen);
     if (rc) return rc;
-    const int ndev = (int)ctx->devs.size();
     FindKTally kt;
     rc = find_k_core(ctx, m, mlen, lo, hi, target, k, &kt, recs);
     if (rc) return rc;
     const FindTally& tally = kt.t;
-    const uint64_t records = kt.records;
-    const bool overflow = kt.overflow;
     hm_find_k_stats st{};
     st.kernel_ms = tally.kernel_ms;
     st.nonces_enqueued = tally.nonces;
     st.tasks_total = tally.tasks;
     st.tasks_run = tally.run;
-    st.records = records;
+    st.records = kt.records;
     st.launches = tally.launches;
-    st.ndev = ndev;
     st.found = (int32_t)recs->size();
-    st.fallback = overflow ? 1 : 0;
-    st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
-                     .count();
-    ctx->last_find_k = st;
-    ctx->have_find_k_stats = true;
+    st.fallback = kt.overflow ? 1 : 0;
+    publish(ctx, ctx->find_k_stats, st, t0);
     return HM_OK;
 }
 

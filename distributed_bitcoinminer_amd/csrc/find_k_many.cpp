@@ -204,9 +204,8 @@ int find_k_many_locked(hm_ctx* ctx, const hm_find_k_request* reqs, int n,
         c += m;
     }
     for (int r = 0; r < n; ++r) st.found += (*recs)[r].size();
-    batch_close(ctx, n, t0, &st);
-    ctx->last_find_k_many = st;
-    ctx->have_find_k_many_stats = true;
+    st.requests = n;
+    publish(ctx, ctx->find_k_many_stats, st, t0);
     return HM_OK;
 }
 

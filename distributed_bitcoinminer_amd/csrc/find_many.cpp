@@ -105,9 +105,8 @@ int find_many_locked(hm_ctx* ctx, const hm_find_request* reqs, int n, hm_result*
         if (rc) return drain_streams(ctx, rc);
     }
     for (int r = 0; r < n; ++r) st.found += found[r];
-    batch_close(ctx, n, t0, &st);
-    ctx->last_find_many = st;
-    ctx->have_find_many_stats = true;
+    st.requests = n;
+    publish(ctx, ctx->find_many_stats, st, t0);
     return HM_OK;
 }
 

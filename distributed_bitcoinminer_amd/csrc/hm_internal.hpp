@@ -2,11 +2,12 @@
 // state (Device), the context (hm_ctx), the constants, and the helpers each
 // file exports to the others.  Not part of the ABI (include/hipminer.h).
 //
+//   plan.hpp      the planner; guarded() and msg_or_empty(), which host_scan.cpp shares
 //   device.cpp    device and context lifetime, host_wait / host_read, K+W table growth, deadlines
 //   seg_walk.cpp  one segment -> its sequence of launches (SegWalk), the argument fillers
 //   scan.cpp      hm_scan_many: batching, the fused launch, merge, stats
-//   find.cpp      hm_find
-//   find_k.cpp    hm_find_k
+//   find.cpp      hm_find; the early-exit walk's steps (find_walk, below, runs them)
+//   find_k.cpp    hm_find_k, over the same walk
 //   collect.cpp   hm_collect
 //   batch.cpp     the chunk runner of the three batch calls below: plan, prepare, launch, wait and read
 //   find_many.cpp hm_find_many
@@ -15,6 +16,8 @@
 //   verify.cpp    hm_hash_many, hm_verify
 //   verify_many.cpp hm_verify_many
 //   api.cpp       the extern "C" entry points and the debug exports
+// Every family's stats record is a StatsSlot of hm_ctx: publish() fills it when
+// a call succeeds, stats_out() is its hm_X_stats_sized.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -67,20 +70,6 @@ constexpr uint64_t kFindGenericNonces = 1ull << 30;  // per generic launch
 // hm_hash_many and hm_verify (verify.cpp): list elements per chunk and device
 // (one copy in, one launch; HM_OPT_VERIFY_CHUNK)
 constexpr uint32_t kVerifyChunk = 1u << 22;
-
-// No C++ exception crosses the C ABI (include/hipminer.h): the entry points
-// run their bodies through guarded(), which maps an escaping exception
-// (std::bad_alloc from the planner's vectors, anything else) to a return code.
-template <typename F>
-int guarded(F&& f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc&) {
-        return HM_ERR_NOMEM;
-    } catch (...) {
-        return HM_ERR_INTERNAL;
-    }
-}
 
 struct Launch {
     hipEvent_t start, stop;
@@ -180,6 +169,13 @@ int hip_fail(hipError_t e, const char* what);
         if (e_ != hipSuccess) return hm::hip_fail(e_, #expr); \
     } while (0)
 
+// A family's stats record: the last successful call's, once there was one.
+template <class T>
+struct StatsSlot {
+    bool have = false;
+    T v{};
+};
+
 }  // namespace hm
 
 struct hm_ctx {
@@ -219,28 +215,47 @@ struct hm_ctx {
     std::chrono::steady_clock::time_point deadline_at{};
     double deadline_ms = 0;  // the current call's deadline (hm_stats.deadline_ms)
     bool abandoned = false;
-    bool have_stats = false;
     int merge = HM_MERGE_NONE;  // how the current call merged device results
-    hm_stats last{};
-    bool have_find_stats = false;  // hm_find keeps its own record: `last` stays the last scan's
-    hm_find_stats last_find{};
-    bool have_collect_stats = false;  // and so does hm_collect
-    hm_collect_stats last_collect{};
-    bool have_verify_stats = false;  // and hm_hash_many / hm_verify
-    hm_verify_stats last_verify{};
-    bool have_find_many_stats = false;  // and hm_find_many
-    hm_find_many_stats last_find_many{};
-    bool have_verify_many_stats = false;  // and hm_verify_many
-    hm_verify_many_stats last_verify_many{};
-    bool have_collect_many_stats = false;  // and hm_collect_many
-    hm_collect_many_stats last_collect_many{};
-    bool have_find_k_stats = false;  // and hm_find_k
-    hm_find_k_stats last_find_k{};
-    bool have_find_k_many_stats = false;  // and hm_find_k_many
-    hm_find_k_many_stats last_find_k_many{};
+    // every family keeps its own record: hm_find leaves the last scan's alone
+    hm::StatsSlot<hm_stats> scan_stats;
+    hm::StatsSlot<hm_find_stats> find_stats;
+    hm::StatsSlot<hm_collect_stats> collect_stats;
+    hm::StatsSlot<hm_verify_stats> verify_stats;  // hm_hash_many and hm_verify
+    hm::StatsSlot<hm_find_many_stats> find_many_stats;
+    hm::StatsSlot<hm_verify_many_stats> verify_many_stats;
+    hm::StatsSlot<hm_collect_many_stats> collect_many_stats;
+    hm::StatsSlot<hm_find_k_stats> find_k_stats;
+    hm::StatsSlot<hm_find_k_many_stats> find_k_many_stats;
 };
 
 namespace hm {
+
+// hm_X_stats_sized: the first min(size, sizeof(T)) bytes of the slot's record.  A caller built
+// against an older header passes its smaller struct (the layouts only ever grow at the end);
+// min_size is the family's first layout.
+template <class T>
+int stats_out(const hm_ctx* ctx, StatsSlot<T> hm_ctx::*slot, T* out, size_t size, size_t min_size) {
+    if (!ctx || !out || size < min_size) return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);  // calls write their slot under the lock
+    if (!(ctx->*slot).have) return HM_ERR_INVALID;
+    memcpy(out, &(ctx->*slot).v, std::min(size, sizeof(T)));
+    return HM_OK;
+}
+// The close of a successful call that began at t0 (ctx->mu held): st, with the
+// two fields every family has, becomes the slot's record.
+template <class T>
+void publish(hm_ctx* ctx, StatsSlot<T>& slot, T st, std::chrono::steady_clock::time_point t0) {
+    st.ndev = (int)ctx->devs.size();
+    st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
+                     .count();
+    slot.v = st;
+    slot.have = true;
+}
+// A control block of `words` words on the current device, made on first use.
+inline int ctl_block(uint64_t** p, size_t words) {
+    if (!*p) HIPCHK(hipMalloc(p, words * sizeof(uint64_t)));
+    return HM_OK;
+}
 
 // ---- device.cpp ----
 int open_devices(const int* devices, int ndev, hm_ctx** out);
@@ -512,6 +527,55 @@ int find_issue(hm_ctx* ctx, Device& dv, FindDev& fd, const MsgPlan& mp, Family f
 // control words at dev_ctl back into fd.ctl.
 int find_collect(hm_ctx* ctx, Device& dv, FindDev& fd, FindTally& tally, const uint64_t* dev_ctl,
                  int nwords);
+// The walk of hm_find and hm_find_k over [lo, hi] (find.cpp has the rules): pieces in ascending
+// order; within a piece each device issues up to kFindLookahead launches of `family` with the
+// trailer make(dv, launch_lo), then its first `nwords` control words at dv.*ctl are read back
+// into fds[i].ctl and *best, the pruning bound, is lowered to word 0, the stop word.  It ends
+// once *best is set or nothing is left.  The caller has reset the control words on stream 0.
+// Every failure leaves through drain_failed.
+template <typename Make>
+int find_walk(hm_ctx* ctx, const MsgPlan& mp, uint64_t lo, uint64_t hi, Family family,
+              uint64_t* Device::*ctl, int nwords, std::vector<FindDev>& fds, FindTally& tally,
+              uint64_t* best, Make&& make) {
+    static_assert(kFkStop == 0, "the stop word is the first of the control words");
+    const int ndev = (int)ctx->devs.size();
+    *best = ~0ull;
+    PieceWalk pieces(ctx, mp, lo, hi);
+    std::vector<std::vector<SegPlan>> shards;
+    // later pieces lie above a hit (hm_find_k: above every record written so far, the bound
+    // among them)
+    while (*best == ~0ull && pieces.next(&shards)) {
+        for (int i = 0; i < ndev; ++i) {
+            fds[i].segs = std::move(shards[i]);
+            fds[i].si = 0;
+            fds[i].seg_open = false;
+        }
+        for (;;) {
+            bool any = false;
+            for (int i = 0; i < ndev; ++i) {
+                Device& dv = ctx->devs[i];
+                if (hipSetDevice(dv.ordinal) != hipSuccess) return drain_failed(ctx, HM_ERR_HIP);
+                while (fds[i].inflight < kFindLookahead) {
+                    bool issued = false;
+                    int rc = find_issue(ctx, dv, fds[i], mp, family, *best, tally, &issued,
+                                        [&](uint64_t launch_lo) { return make(dv, launch_lo); });
+                    if (rc) return drain_failed(ctx, rc);
+                    if (!issued) break;
+                }
+                any = any || fds[i].inflight > 0;
+            }
+            if (!any) break;
+            for (int i = 0; i < ndev; ++i) {
+                if (!fds[i].inflight) continue;
+                Device& dv = ctx->devs[i];
+                int rc = find_collect(ctx, dv, fds[i], tally, dv.*ctl, nwords);
+                if (rc) return drain_failed(ctx, rc);
+                *best = std::min(*best, fds[i].ctl[0]);
+            }
+        }
+    }
+    return HM_OK;
+}
 
 // ---- find_k.cpp: hm_find_k without its opening and its stats, for hm_find_k_many's fallback ----
 struct FindKTally {
@@ -538,9 +602,6 @@ struct CollectTally {
 int collect_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_t hi,
                  uint64_t target, size_t cap, CollectTally* tally, std::vector<hm_result>* recs,
                  uint64_t* total);
-// Make dv's record buffer hold `cap` records (grown by at least doubling, the
-// old one retired).
-int collect_buffer(Device& dv, size_t cap);
 // Records as a device handed them out, in dispatch order: sorted by nonce, then
 // HM_ERR_INTERNAL on a duplicate, a nonce outside [lo, hi] or a hash at or
 // above target.
@@ -649,14 +710,6 @@ int batch_open(hm_ctx* ctx, const Req* reqs, int n, std::chrono::steady_clock::t
     for (Device& dv : ctx->devs) dv.evnext = 0;
     return HM_OK;
 }
-// The part of a batch call's stats record every family has.
-template <typename Stats>
-void batch_close(const hm_ctx* ctx, int n, std::chrono::steady_clock::time_point t0, Stats* st) {
-    st->requests = n;
-    st->ndev = (int)ctx->devs.size();
-    st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
-                      .count();
-}
 // A batch call that fails with rc leaves nothing queued: unless rc is a
 // timeout, every stream the devices have made is waited for, then
 // drain_failed (stream 0 and the events).  Returns rc.
@@ -690,8 +743,9 @@ int list_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, const uint64_t* non
                 std::vector<uint64_t>* out, uint64_t* bad);
 // Make *buf hold `want` units of `unit` bytes of device memory (*have: what it
 // holds now).  A larger one replaces it -- at least twice the old size, at most
-// `most` units -- and the old one is kept until hm_close, as collect.cpp's
-// record buffer.
+// `most` units, so all the buffers a device retires together are smaller than
+// its current one -- and the old one is kept until hm_close, as the K+W tables
+// are (hipFree would wait for the whole device).
 template <typename T>
 int grow_buffer(Device& dv, T** buf, size_t* have, size_t want, size_t most, size_t unit) {
     if (want <= *have) return HM_OK;
@@ -705,6 +759,11 @@ int grow_buffer(Device& dv, T** buf, size_t* have, size_t want, size_t most, siz
     *buf = b;
     *have = size;
     return HM_OK;
+}
+// Make dv's record buffer (hm_collect, hm_find_k and their batch forms) hold `cap` records.
+inline int collect_buffer(Device& dv, size_t cap) {
+    return grow_buffer(dv, &dv.collect_buf, &dv.collect_cap, cap, HM_COLLECT_CAP_MAX,
+                       sizeof(hm_result));
 }
 // hm_verify_many: per[i] for i < nreq, *refs (the bad (request, index) pairs,
 // ascending, when *bad <= cap; empty otherwise) and *bad.

@@ -127,30 +127,35 @@ CompressFn pick_compress() {
     return compress_c;
 }
 
+// The tail blocks of nonce x (d digits) behind the midstate: r prefix bytes,
+// the digits, 0x80, zeros and the 64-bit bit length fill tail[0 .. 64 * nb).
+// Returns nb (1 or 2); the last digit is tail[r + d - 1].
+uint32_t build_tail(const MsgPlan& mp, uint64_t x, uint32_t d, uint8_t tail[128]) {
+    const uint32_t r = mp.r, T = r + d;
+    memset(tail, 0, 128);
+    for (uint32_t i = 0; i < r; ++i) tail[i] = (uint8_t)(mp.pw[i / 4] >> (24 - 8 * (i % 4)));
+    for (uint32_t k = 0; k < d; ++k) {
+        tail[T - 1 - k] = (uint8_t)('0' + x % 10);
+        x /= 10;
+    }
+    tail[T] = 0x80;
+    const uint32_t nb = T + 9 <= 64 ? 1 : 2;
+    const uint64_t bits = (mp.len + 1 + d) * 8;
+    for (int i = 0; i < 8; ++i) tail[64 * nb - 1 - i] = (uint8_t)(bits >> (8 * i));
+    return nb;
+}
+
 // Walk [a, b] (a <= b, one thread) in ascending order, every digit segment of
 // it in turn: visit(key, nonce) per nonce; a true return ends the walk.
 template <typename Visit>
 void walk_chunk(const MsgPlan& mp, uint64_t a, uint64_t b, CompressFn compress, Visit&& visit) {
-    const uint32_t r = mp.r;
     for (uint32_t d = digits_u64(a); d <= digits_u64(b); ++d) {
         const uint64_t dlo = d == 1 ? 0 : pow10_u64(d - 1);
         const uint64_t dhi = d == 20 ? ~0ull : pow10_u64(d) - 1;
         const uint64_t slo = std::max(a, dlo), shi = std::min(b, dhi);
         if (slo > shi) continue;
-        // tail: r prefix bytes, d digits, 0x80, zeros, 64-bit bit length
         uint8_t tail[128];
-        memset(tail, 0, sizeof tail);
-        for (uint32_t i = 0; i < r; ++i) tail[i] = (uint8_t)(mp.pw[i / 4] >> (24 - 8 * (i % 4)));
-        uint64_t x = slo;
-        for (uint32_t k = 0; k < d; ++k) {
-            tail[r + d - 1 - k] = (uint8_t)('0' + x % 10);
-            x /= 10;
-        }
-        const uint32_t T = r + d;
-        tail[T] = 0x80;
-        const uint32_t nb = T + 9 <= 64 ? 1 : 2;
-        const uint64_t bits = (mp.len + 1 + d) * 8;
-        for (int i = 0; i < 8; ++i) tail[64 * nb - 1 - i] = (uint8_t)(bits >> (8 * i));
+        const uint32_t nb = build_tail(mp, slo, d, tail), T = mp.r + d;
         const uint8_t* last = tail + 64 * (nb - 1);
         uint32_t s0[8];  // state entering the last tail block
         if (nb == 2) compress(mp.mid, tail, s0);
@@ -294,20 +299,8 @@ void collect_chunk(const MsgPlan& mp, uint64_t a, uint64_t b, uint64_t target, s
 // Hash(msg, n) of one nonce from the midstate: the tail bytes of walk_chunk,
 // built for n alone, and one or two compressions.
 uint64_t hash_from_mid(const MsgPlan& mp, uint64_t n, CompressFn compress) {
-    const uint32_t r = mp.r, d = digits_u64(n);
     uint8_t tail[128];
-    memset(tail, 0, sizeof tail);
-    for (uint32_t i = 0; i < r; ++i) tail[i] = (uint8_t)(mp.pw[i / 4] >> (24 - 8 * (i % 4)));
-    uint64_t x = n;
-    for (uint32_t k = 0; k < d; ++k) {
-        tail[r + d - 1 - k] = (uint8_t)('0' + x % 10);
-        x /= 10;
-    }
-    const uint32_t T = r + d;
-    tail[T] = 0x80;
-    const uint32_t nb = T + 9 <= 64 ? 1 : 2;
-    const uint64_t bits = (mp.len + 1 + d) * 8;
-    for (int i = 0; i < 8; ++i) tail[64 * nb - 1 - i] = (uint8_t)(bits >> (8 * i));
+    const uint32_t nb = build_tail(mp, n, digits_u64(n), tail);
     uint32_t s[8], o[8];
     if (nb == 2) compress(mp.mid, tail, s);
     else memcpy(s, mp.mid, sizeof s);
@@ -425,6 +418,63 @@ int over_list(size_t n, int threads, Prepare&& prepare, Work&& work) {
     return rc;
 }
 
+// The same over the nonces of [lo, hi] (lo <= hi; up to 2^64 of them, so the
+// count is 128-bit): work(t, a, b) over the inclusive [a, b], contiguous,
+// near-equal and ascending in t; ranges below 4096 nonces per thread use fewer.
+template <typename Prepare, typename Work>
+int over_range(uint64_t lo, uint64_t hi, int threads, Prepare&& prepare, Work&& work) {
+    typedef unsigned __int128 u128;
+    const u128 count = (u128)(hi - lo) + 1;
+    unsigned n = threads > 0 ? (unsigned)threads : default_threads();
+    n = std::min(n, 1024u);
+    if (count < (u128)n * 4096) n = (unsigned)std::max<u128>(1, count / 4096);
+    prepare(n);
+    std::vector<std::thread> pool;
+    pool.reserve(n);
+    const u128 per = count / n, extra = count % n;
+    u128 start = 0;
+    int rc = HM_OK;
+    for (unsigned t = 0; t < n; ++t) {
+        const u128 len_t = per + (t < extra ? 1 : 0);
+        const uint64_t a = lo + (uint64_t)start, b = lo + (uint64_t)(start + len_t - 1);
+        start += len_t;
+        if (t + 1 == n) {
+            work(t, a, b);  // the calling thread
+            break;
+        }
+        try {
+            pool.emplace_back(work, t, a, b);
+        } catch (...) {  // no thread: join the started ones before failing
+            rc = HM_ERR_INTERNAL;
+            break;
+        }
+    }
+    for (auto& th : pool) th.join();
+    return rc;
+}
+
+// hm_find_cpu's and hm_find_k_cpu's pool over the (hi - lo) / kFindWindow + 1
+// <= 2^50 windows of [lo, hi]: worker(nwin) on at most one thread per window,
+// the last on the calling thread.  The workers share the windows, so threads
+// that fail to start are made up for by the started ones and the caller.
+template <typename Worker>
+void over_windows(uint64_t lo, uint64_t hi, int threads, Worker&& worker) {
+    const uint64_t nwin = (hi - lo) / kFindWindow + 1;
+    unsigned n = threads > 0 ? (unsigned)threads : default_threads();
+    n = (unsigned)std::min<uint64_t>(std::min(n, 1024u), nwin);
+    std::vector<std::thread> pool;
+    pool.reserve(n);
+    for (unsigned t = 0; t + 1 < n; ++t) {
+        try {
+            pool.emplace_back(worker, nwin);
+        } catch (...) {
+            break;
+        }
+    }
+    worker(nwin);  // the calling thread
+    for (auto& th : pool) th.join();
+}
+
 }  // namespace
 }  // namespace hm
 
@@ -432,140 +482,76 @@ extern "C" int hm_scan_cpu(const uint8_t* msg, size_t len, uint64_t lo, uint64_t
                            hm_result* out) {
     using namespace hm;
     if (!out || (!msg && len)) return HM_ERR_INVALID;
-    try {
+    return guarded([&] {
         if (lo > hi) {
             *out = hm_result{~0ull, 0};
             return HM_OK;
         }
-        static const uint8_t empty = 0;
-        const MsgPlan mp = plan_message(msg ? msg : &empty, msg ? len : 0);
+        const MsgPlan mp = plan_message(msg_or_empty(msg, len));
         const CompressFn compress = pick_compress();
-        typedef unsigned __int128 u128;
-        const u128 count = (u128)(hi - lo) + 1;
-        unsigned n = threads > 0 ? (unsigned)threads : default_threads();
-        n = std::min(n, 1024u);
-        if (count < (u128)n * 4096) n = (unsigned)std::max<u128>(1, count / 4096);
-        std::vector<Best> part(n);
-        std::vector<std::thread> pool;
-        pool.reserve(n);
-        const u128 per = count / n, extra = count % n;
-        u128 start = 0;
-        int rc = HM_OK;
-        for (unsigned t = 0; t < n; ++t) {
-            const u128 len_t = per + (t < extra ? 1 : 0);
-            const uint64_t a = lo + (uint64_t)start, b = lo + (uint64_t)(start + len_t - 1);
-            start += len_t;
-            if (t + 1 == n) {
-                scan_chunk(mp, a, b, compress, &part[t]);  // the calling thread
-                break;
-            }
-            try {
-                pool.emplace_back(scan_chunk, std::cref(mp), a, b, compress, &part[t]);
-            } catch (...) {  // no thread: join the started ones before failing
-                rc = HM_ERR_INTERNAL;
-                break;
-            }
-        }
-        for (auto& th : pool) th.join();
+        std::vector<Best> part;
+        const int rc = over_range(
+            lo, hi, threads, [&](unsigned parts) { part.resize(parts); },
+            [&](unsigned t, uint64_t a, uint64_t b) { scan_chunk(mp, a, b, compress, &part[t]); });
         if (rc) return rc;
         Best best;
         for (const Best& p : part) best.take(p.key, p.nonce);
         *out = hm_result{best.key, best.nonce};
         return HM_OK;
-    } catch (const std::bad_alloc&) {
-        return HM_ERR_NOMEM;
-    } catch (...) {
-        return HM_ERR_INTERNAL;
-    }
+    });
 }
 
 extern "C" int hm_find_cpu(const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
                            uint64_t target, int threads, hm_result* out, int* found) {
     using namespace hm;
     if (!out || !found || (!msg && len)) return HM_ERR_INVALID;
-    try {
+    return guarded([&] {
         if (lo > hi || target == 0) {
             *out = hm_result{~0ull, 0};
             *found = 0;
             return HM_OK;
         }
-        static const uint8_t empty = 0;
-        const uint8_t* m = msg ? msg : &empty;
-        const uint64_t mlen = msg ? len : 0;
-        const MsgPlan mp = plan_message(m, mlen);
+        const Msg m = msg_or_empty(msg, len);
+        const MsgPlan mp = plan_message(m);
         const CompressFn compress = pick_compress();
-        // windows of [lo, hi]: (hi - lo) / kFindWindow + 1 <= 2^50
-        const uint64_t nwin = (hi - lo) / kFindWindow + 1;
-        unsigned n = threads > 0 ? (unsigned)threads : default_threads();
-        n = (unsigned)std::min<uint64_t>(std::min(n, 1024u), nwin);
         FindShared sh;
-        std::vector<std::thread> pool;
-        pool.reserve(n);
-        for (unsigned t = 0; t + 1 < n; ++t) {
-            try {
-                pool.emplace_back(find_worker, std::cref(mp), lo, hi, target, nwin, compress, &sh);
-            } catch (...) {  // no thread: the started ones and the caller do the work
-                break;
-            }
-        }
-        find_worker(mp, lo, hi, target, nwin, compress, &sh);  // the calling thread
-        for (auto& th : pool) th.join();
+        over_windows(lo, hi, threads, [&](uint64_t nwin) {
+            find_worker(mp, lo, hi, target, nwin, compress, &sh);
+        });
         if (sh.hit.load()) {
             const uint64_t nn = sh.best.load();
-            *out = hm_result{host_hash(m, mlen, nn), nn};
+            *out = hm_result{host_hash(m.p, m.len, nn), nn};
             *found = 1;
         } else {
             *out = hm_result{~0ull, 0};
             *found = 0;
         }
         return HM_OK;
-    } catch (const std::bad_alloc&) {
-        return HM_ERR_NOMEM;
-    } catch (...) {
-        return HM_ERR_INTERNAL;
-    }
+    });
 }
 
 extern "C" int hm_find_k_cpu(const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
                              uint64_t target, size_t k, int threads, hm_result* out, size_t* n) {
     using namespace hm;
     if (!out || !n || (!msg && len) || k == 0 || k > HM_FIND_K_MAX) return HM_ERR_INVALID;
-    try {
+    return guarded([&] {
         if (lo > hi || target == 0) {
             *n = 0;
             return HM_OK;
         }
-        static const uint8_t empty = 0;
-        const MsgPlan mp = plan_message(msg ? msg : &empty, msg ? len : 0);
+        const MsgPlan mp = plan_message(msg_or_empty(msg, len));
         const CompressFn compress = pick_compress();
-        // windows and threads as hm_find_cpu's
-        const uint64_t nwin = (hi - lo) / kFindWindow + 1;
-        unsigned nt = threads > 0 ? (unsigned)threads : default_threads();
-        nt = (unsigned)std::min<uint64_t>(std::min(nt, 1024u), nwin);
         FindKShared sh;
-        std::vector<std::thread> pool;
-        pool.reserve(nt);
-        for (unsigned t = 0; t + 1 < nt; ++t) {
-            try {
-                pool.emplace_back(find_k_worker, std::cref(mp), lo, hi, target, k, nwin, compress,
-                                  &sh);
-            } catch (...) {  // no thread: the started ones and the caller do the work
-                break;
-            }
-        }
-        find_k_worker(mp, lo, hi, target, k, nwin, compress, &sh);  // the calling thread
-        for (auto& th : pool) th.join();
+        over_windows(lo, hi, threads, [&](uint64_t nwin) {
+            find_k_worker(mp, lo, hi, target, k, nwin, compress, &sh);
+        });
         if (sh.failed) return HM_ERR_NOMEM;
         std::sort(sh.recs.begin(), sh.recs.end(),
                   [](const hm_result& x, const hm_result& y) { return x.nonce < y.nonce; });
         if (!sh.recs.empty()) memcpy(out, sh.recs.data(), sh.recs.size() * sizeof(hm_result));
         *n = sh.recs.size();
         return HM_OK;
-    } catch (const std::bad_alloc&) {
-        return HM_ERR_NOMEM;
-    } catch (...) {
-        return HM_ERR_INTERNAL;
-    }
+    });
 }
 
 // hm_find_many's answers on the host (ABI 1.13): hm_find_cpu request by
@@ -575,7 +561,7 @@ extern "C" int hm_find_many_cpu(const hm_find_request* reqs, int n, int threads,
     if (n < 0 || (n > 0 && (!reqs || !outs || !found))) return HM_ERR_INVALID;
     for (int r = 0; r < n; ++r)
         if (!reqs[r].msg && reqs[r].len) return HM_ERR_INVALID;
-    try {
+    return hm::guarded([&] {
         std::vector<hm_result> res((size_t)n);
         std::vector<int> hit((size_t)n);
         for (int r = 0; r < n; ++r) {
@@ -589,11 +575,7 @@ extern "C" int hm_find_many_cpu(const hm_find_request* reqs, int n, int threads,
             found[r] = hit[r];
         }
         return HM_OK;
-    } catch (const std::bad_alloc&) {
-        return HM_ERR_NOMEM;
-    } catch (...) {
-        return HM_ERR_INTERNAL;
-    }
+    });
 }
 
 // hm_find_k_many's answers on the host (ABI 1.17): hm_find_k_cpu request by
@@ -604,7 +586,7 @@ extern "C" int hm_find_k_many_cpu(const hm_find_k_request* reqs, int n, int thre
     for (int r = 0; r < n; ++r)
         if ((!reqs[r].msg && reqs[r].len) || reqs[r].k == 0 || reqs[r].k > HM_FIND_K_MAX)
             return HM_ERR_INVALID;
-    try {
+    return hm::guarded([&] {
         std::vector<std::vector<hm_result>> res((size_t)n);
         for (int r = 0; r < n; ++r) {
             const hm_find_k_request& q = reqs[r];
@@ -624,11 +606,7 @@ extern "C" int hm_find_k_many_cpu(const hm_find_k_request* reqs, int n, int thre
             off += reqs[r].k;
         }
         return HM_OK;
-    } catch (const std::bad_alloc&) {
-        return HM_ERR_NOMEM;
-    } catch (...) {
-        return HM_ERR_INTERNAL;
-    }
+    });
 }
 
 extern "C" int hm_collect_cpu(const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
@@ -637,43 +615,20 @@ extern "C" int hm_collect_cpu(const uint8_t* msg, size_t len, uint64_t lo, uint6
     using namespace hm;
     if (!total || (!msg && len) || cap > HM_COLLECT_CAP_MAX || (cap && !out))
         return HM_ERR_INVALID;
-    try {
+    return guarded([&] {
         if (lo > hi || target == 0) {
             *total = 0;
             return HM_OK;
         }
-        static const uint8_t empty = 0;
-        const MsgPlan mp = plan_message(msg ? msg : &empty, msg ? len : 0);
+        const MsgPlan mp = plan_message(msg_or_empty(msg, len));
         const CompressFn compress = pick_compress();
         // contiguous, near-equal chunks in ascending order, as hm_scan_cpu's
-        typedef unsigned __int128 u128;
-        const u128 count = (u128)(hi - lo) + 1;
-        unsigned n = threads > 0 ? (unsigned)threads : default_threads();
-        n = std::min(n, 1024u);
-        if (count < (u128)n * 4096) n = (unsigned)std::max<u128>(1, count / 4096);
-        std::vector<CollectPart> part(n);
-        std::vector<std::thread> pool;
-        pool.reserve(n);
-        const u128 per = count / n, extra = count % n;
-        u128 start = 0;
-        int rc = HM_OK;
-        for (unsigned t = 0; t < n; ++t) {
-            const u128 len_t = per + (t < extra ? 1 : 0);
-            const uint64_t a = lo + (uint64_t)start, b = lo + (uint64_t)(start + len_t - 1);
-            start += len_t;
-            if (t + 1 == n) {
-                collect_chunk(mp, a, b, target, cap, compress, &part[t]);  // the calling thread
-                break;
-            }
-            try {
-                pool.emplace_back(collect_chunk, std::cref(mp), a, b, target, cap, compress,
-                                  &part[t]);
-            } catch (...) {  // no thread: join the started ones before failing
-                rc = HM_ERR_INTERNAL;
-                break;
-            }
-        }
-        for (auto& th : pool) th.join();
+        std::vector<CollectPart> part;
+        const int rc = over_range(
+            lo, hi, threads, [&](unsigned parts) { part.resize(parts); },
+            [&](unsigned t, uint64_t a, uint64_t b) {
+                collect_chunk(mp, a, b, target, cap, compress, &part[t]);
+            });
         if (rc) return rc;
         uint64_t sum = 0;
         for (const CollectPart& p : part) {
@@ -690,11 +645,7 @@ extern "C" int hm_collect_cpu(const uint8_t* msg, size_t len, uint64_t lo, uint6
         }
         *total = sum;
         return HM_OK;
-    } catch (const std::bad_alloc&) {
-        return HM_ERR_NOMEM;
-    } catch (...) {
-        return HM_ERR_INTERNAL;
-    }
+    });
 }
 
 extern "C" int hm_collect_many_cpu(const hm_collect_request* reqs, int n, int threads,
@@ -705,7 +656,7 @@ extern "C" int hm_collect_many_cpu(const hm_collect_request* reqs, int n, int th
         return HM_ERR_INVALID;
     for (int r = 0; r < n; ++r)
         if (!reqs[r].msg && reqs[r].len) return HM_ERR_INVALID;
-    try {
+    return hm::guarded([&] {
         // request-major: request r's records go behind those of the requests
         // before it, into what is left of `cap`; once one does not fit the call
         // has overflowed and the rest are counts
@@ -726,21 +677,16 @@ extern "C" int hm_collect_many_cpu(const hm_collect_request* reqs, int n, int th
         if (sum <= cap && sum) memcpy(out, all.data(), (size_t)sum * sizeof(hm_result));
         *total = sum;
         return HM_OK;
-    } catch (const std::bad_alloc&) {
-        return HM_ERR_NOMEM;
-    } catch (...) {
-        return HM_ERR_INTERNAL;
-    }
+    });
 }
 
 extern "C" int hm_hash_many_cpu(const uint8_t* msg, size_t len, const uint64_t* nonces, size_t n,
                                 int threads, uint64_t* hashes) {
     using namespace hm;
     if ((!msg && len) || (n && (!nonces || !hashes))) return HM_ERR_INVALID;
-    try {
+    return guarded([&] {
         if (n == 0) return HM_OK;
-        static const uint8_t empty = 0;
-        const MsgPlan mp = plan_message(msg ? msg : &empty, msg ? len : 0);
+        const MsgPlan mp = plan_message(msg_or_empty(msg, len));
         const CompressFn compress = pick_compress();
         // every element is written by exactly one thread; a failed start of a
         // thread leaves a prefix written, so the answer goes through a copy
@@ -751,11 +697,7 @@ extern "C" int hm_hash_many_cpu(const uint8_t* msg, size_t len, const uint64_t* 
         if (rc) return rc;
         memcpy(hashes, out.data(), n * sizeof(uint64_t));
         return HM_OK;
-    } catch (const std::bad_alloc&) {
-        return HM_ERR_NOMEM;
-    } catch (...) {
-        return HM_ERR_INTERNAL;
-    }
+    });
 }
 
 extern "C" int hm_verify_cpu(const uint8_t* msg, size_t len, const hm_result* recs, size_t n,
@@ -764,13 +706,12 @@ extern "C" int hm_verify_cpu(const uint8_t* msg, size_t len, const hm_result* re
     using namespace hm;
     if (!bad || (!msg && len) || (n && !recs) || cap > HM_VERIFY_CAP_MAX || (cap && !bad_idx))
         return HM_ERR_INVALID;
-    try {
+    return guarded([&] {
         if (n == 0) {
             *bad = 0;
             return HM_OK;
         }
-        static const uint8_t empty = 0;
-        const MsgPlan mp = plan_message(msg ? msg : &empty, msg ? len : 0);
+        const MsgPlan mp = plan_message(msg_or_empty(msg, len));
         const CompressFn compress = pick_compress();
         std::vector<VerifyPart> part;
         const int rc = over_list(
@@ -794,11 +735,7 @@ extern "C" int hm_verify_cpu(const uint8_t* msg, size_t len, const hm_result* re
         }
         *bad = sum;
         return HM_OK;
-    } catch (const std::bad_alloc&) {
-        return HM_ERR_NOMEM;
-    } catch (...) {
-        return HM_ERR_INTERNAL;
-    }
+    });
 }
 
 extern "C" int hm_verify_many_cpu(const hm_verify_request* reqs, int nreq, int threads,
@@ -810,7 +747,7 @@ extern "C" int hm_verify_many_cpu(const hm_verify_request* reqs, int nreq, int t
         return HM_ERR_INVALID;
     for (int r = 0; r < nreq; ++r)
         if ((!reqs[r].msg && reqs[r].len) || (!reqs[r].recs && reqs[r].n)) return HM_ERR_INVALID;
-    try {
+    return guarded([&] {
         // the flattened sequence: request i holds positions [start[i], start[i + 1])
         std::vector<uint64_t> start((size_t)nreq + 1, 0);
         for (int i = 0; i < nreq; ++i) {
@@ -822,12 +759,9 @@ extern "C" int hm_verify_many_cpu(const hm_verify_request* reqs, int nreq, int t
         std::vector<VerifyManyPart> part;
         uint64_t sum = 0;
         if (total > 0) {
-            static const uint8_t empty = 0;
             std::vector<MsgPlan> plans((size_t)nreq);
             for (int i = 0; i < nreq; ++i)
-                if (reqs[i].n)
-                    plans[i] = plan_message(reqs[i].msg ? reqs[i].msg : &empty,
-                                            reqs[i].msg ? reqs[i].len : 0);
+                if (reqs[i].n) plans[i] = plan_message(msg_or_empty(reqs[i].msg, reqs[i].len));
             const CompressFn compress = pick_compress();
             const int rc = over_list(
                 total, threads, [&](unsigned parts) { part.resize(parts); },
@@ -854,9 +788,5 @@ extern "C" int hm_verify_many_cpu(const hm_verify_request* reqs, int nreq, int t
         }
         *bad = sum;
         return HM_OK;
-    } catch (const std::bad_alloc&) {
-        return HM_ERR_NOMEM;
-    } catch (...) {
-        return HM_ERR_INTERNAL;
-    }
+    });
 }

@@ -8,12 +8,40 @@
 // folded into a host midstate.  The remaining "tail" holds r = (len+1) % 64
 // prefix bytes, the d digits, 0x80 and the bit length, in nb (1 or 2) blocks.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
+#include <new>
 #include <string>
 #include <vector>
 
+#include "../../include/hipminer.h"
+
 namespace hm {
+
+// No C++ exception crosses the C ABI (include/hipminer.h): the entry points
+// run their bodies through guarded(), which maps an escaping exception
+// (std::bad_alloc from the planner's vectors, anything else) to a return code.
+template <typename F>
+int guarded(F&& f) {
+    try {
+        return f();
+    } catch (const std::bad_alloc&) {
+        return HM_ERR_NOMEM;
+    } catch (...) {
+        return HM_ERR_INTERNAL;
+    }
+}
+
+// The ABI's null-message rule: a null msg is the empty message, whatever len says.
+struct Msg {
+    const uint8_t* p;
+    size_t len;
+};
+inline Msg msg_or_empty(const uint8_t* msg, size_t len) {
+    static const uint8_t empty = 0;
+    return msg ? Msg{msg, len} : Msg{&empty, 0};
+}
 
 struct MsgPlan {
     uint32_t mid[8];    // midstate after the constant prefix blocks
@@ -46,6 +74,7 @@ struct SegPlan {
 uint32_t digits_u64(uint64_t n);
 uint64_t pow10_u64(uint32_t k);  // k <= 19
 MsgPlan plan_message(const uint8_t* msg, uint64_t len);
+inline MsgPlan plan_message(const Msg& m) { return plan_message(m.p, m.len); }
 // Segment list for inclusive [lo, hi] (lo <= hi).  table_digits (1..7, 0 =
 // default 7 = kTableDigits in plan.cpp) caps the final-block digits a chained
 // K+W table covers; -1 turns the chained layout of >= 5 final-block digits

@@ -505,10 +505,9 @@ int scan_chunk(hm_ctx* ctx, const hm_request* reqs, int nreq, hm_result* outs, b
     if (ctx->merge_rccl && !distinct_ordinals(ctx)) return HM_ERR_INVALID;
     std::vector<MsgPlan> plans(nreq);
     std::vector<std::vector<DevReq>> per_dev(ndev, std::vector<DevReq>(nreq));
-    static const uint8_t empty_msg = 0;
     for (int r = 0; r < nreq; ++r) {
         const hm_request& q = reqs[r];
-        plans[r] = plan_message(q.msg ? q.msg : &empty_msg, q.msg ? q.len : 0);
+        plans[r] = plan_message(msg_or_empty(q.msg, q.len));
         // contiguous shards of equal modelled cost
         const std::vector<Shard> sh =
             partition_range(plans[r], q.lo, q.hi, ndev, ctx->force_generic);
@@ -589,10 +588,8 @@ int scan_many_locked(hm_ctx* ctx, const hm_request* reqs, int n, hm_result* outs
         int rc = scan_chunk(ctx, reqs + c, m, res.data() + c, c == 0);
         if (rc) return rc;
     }
-    const int ndev = (int)ctx->devs.size();
     // stats
     hm_stats st{};
-    st.ndev = ndev;
     st.nonces = total;
     // aggregate per kernel instantiation; the dominant one has the most nonces
     struct Agg { std::string name; double ms = 0; uint64_t nonces = 0; int launches = 0;
@@ -656,10 +653,7 @@ int scan_many_locked(hm_ctx* ctx, const hm_request* reqs, int n, hm_result* outs
     st.mid_call_syncs = ctx->mid_syncs;
     st.table_grows = ctx->table_grows;
     st.deadline_ms = ctx->deadline_ms;
-    st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
-                     .count();
-    ctx->last = st;
-    ctx->have_stats = true;
+    publish(ctx, ctx->scan_stats, st, t0);
     for (int r = 0; r < n; ++r) outs[r] = res[r];
     return HM_OK;
 }

@@ -394,9 +394,9 @@ int begin_ranged_call(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, 
                       std::chrono::steady_clock::time_point t0, const uint8_t** m, size_t* mlen) {
     // an abandoned context's devices may still run its timed-out work
     if (ctx->abandoned) return HM_ERR_TIMEOUT;
-    static const uint8_t empty_msg = 0;
-    *m = msg ? msg : &empty_msg;
-    *mlen = msg ? len : 0;
+    const Msg e = msg_or_empty(msg, len);
+    *m = e.p;
+    *mlen = e.len;
     const hm_request whole{*m, *mlen, lo, hi};  // auto models the whole range
     call_deadline(ctx, &whole, 1, t0);
     return HM_OK;

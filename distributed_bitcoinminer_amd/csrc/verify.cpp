@@ -48,9 +48,7 @@ int list_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, const uint64_t* non
     const auto t0 = std::chrono::steady_clock::now();
     // an abandoned context's devices may still run its timed-out work
     if (ctx->abandoned) return HM_ERR_TIMEOUT;
-    static const uint8_t empty_msg = 0;
-    const uint8_t* m = msg ? msg : &empty_msg;
-    const size_t mlen = msg ? len : 0;
+    const Msg m = msg_or_empty(msg, len);
     list_deadline(ctx, n, t0);
     const bool verify = recs != nullptr;
     const size_t unit = verify ? sizeof(hm_result) : sizeof(uint64_t);
@@ -65,7 +63,7 @@ int list_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, const uint64_t* non
     out->clear();
     if (n > 0) {
         if (!verify) out->resize(n);
-        const MsgPlan mp = plan_message(m, mlen);
+        const MsgPlan mp = plan_message(m);
         typedef unsigned __int128 u128;
         for (int i = 0; i < ndev; ++i) {
             lds[i].lo = (size_t)((u128)n * (unsigned)i / (unsigned)ndev);
@@ -83,8 +81,8 @@ int list_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, const uint64_t* non
             if (verify) {
                 rc = grow_buffer(dv, &dv.verify_idx, &dv.verify_idx_cap, cap, HM_VERIFY_CAP_MAX,
                                  sizeof(uint64_t));
+                if (!rc) rc = ctl_block(&dv.verify_ctl, 2);
                 if (rc) return rc;
-                if (!dv.verify_ctl) HIPCHK(hipMalloc(&dv.verify_ctl, 2 * sizeof(uint64_t)));
             }
         }
         for (int i = 0; i < ndev; ++i) {
@@ -107,7 +105,7 @@ int list_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, const uint64_t* non
             ka.cursor = verify ? dv.verify_ctl + 1 : nullptr;
             ka.idx = verify && cap ? dv.verify_idx : nullptr;
             ka.target = target;
-            ka.bits0 = ((uint64_t)mlen + 1) * 8;
+            ka.bits0 = ((uint64_t)m.len + 1) * 8;
             ka.cap = (uint32_t)cap;
             ka.r = mp.r;
             memcpy(ka.pw, mp.pw, sizeof ka.pw);
@@ -207,13 +205,9 @@ int list_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, const uint64_t* non
     vs.copy_ms = copy_ms;
     vs.records = n;
     vs.bad = sum;
-    vs.ndev = ndev;
     vs.overflow = verify && sum > cap ? 1 : 0;
     for (const ListDev& ld : lds) vs.launches += ld.launches;
-    vs.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
-                     .count();
-    ctx->last_verify = vs;
-    ctx->have_verify_stats = true;
+    publish(ctx, ctx->verify_stats, vs, t0);
     *bad = sum;
     return HM_OK;
 }

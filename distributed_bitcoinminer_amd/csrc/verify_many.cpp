@@ -143,7 +143,6 @@ int verify_many_locked(hm_ctx* ctx, const hm_verify_request* reqs, int nreq, siz
     const auto t0 = std::chrono::steady_clock::now();
     // an abandoned context's devices may still run its timed-out work
     if (ctx->abandoned) return HM_ERR_TIMEOUT;
-    static const uint8_t empty_msg = 0;
     const int ndev = (int)ctx->devs.size();
     const uint32_t chunk = ctx->verify_chunk ? ctx->verify_chunk : kVerifyChunk;
     const uint32_t maxjobs = ctx->verify_jobs ? ctx->verify_jobs : kVerifyJobsMax;
@@ -164,9 +163,7 @@ int verify_many_locked(hm_ctx* ctx, const hm_verify_request* reqs, int nreq, siz
     if (total > 0) {
         std::vector<MsgPlan> plans((size_t)nreq);
         for (int i = 0; i < nreq; ++i)
-            if (reqs[i].n)
-                plans[i] = plan_message(reqs[i].msg ? reqs[i].msg : &empty_msg,
-                                        reqs[i].msg ? reqs[i].len : 0);
+            if (reqs[i].n) plans[i] = plan_message(msg_or_empty(reqs[i].msg, reqs[i].len));
         typedef unsigned __int128 u128;
         size_t most = 0;  // launches of the busiest device
         for (int i = 0; i < ndev; ++i) {
@@ -338,12 +335,8 @@ int verify_many_locked(hm_ctx* ctx, const hm_verify_request* reqs, int nreq, siz
     vs.requests = nreq;
     vs.launches = launches;
     vs.copies = launches;  // one blob per launch
-    vs.ndev = ndev;
     vs.overflow = sum > cap ? 1 : 0;
-    vs.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
-                     .count();
-    ctx->last_verify_many = vs;
-    ctx->have_verify_many_stats = true;
+    publish(ctx, ctx->verify_many_stats, vs, t0);
     *bad = sum;
     return HM_OK;
 }

@@ -6,7 +6,9 @@ profiles/batch_dedup/rates.jsonl.
 usage: python tools/batch_dedup_summary.py RAW_DIR [LABEL ...] >> rates.jsonl
 
 RAW_DIR holds one file per tool run, named LABEL.rRUN.TOOL.jsonl (TOOL =
-find_many, collect_many or find_k_many): the stdout of that tree's rate tool.
+find_many, collect_many or find_k_many; for profiles/host_dedup/ also find and
+find_k, tools/find_rate.py and tools/find_k_rate.py): the stdout of that tree's
+rate tool.
 The labels `parent` and `parent2` are the parent commit's tree run twice (the
 second gives the A/A spread on identical code); every other LABEL (default:
 all found) is a tree under test.  A label is judged against the parent runs
@@ -29,9 +31,9 @@ import statistics
 import sys
 
 KEY = ("part", "msg", "what", "target", "n", "k", "lo", "hi", "cap")
-MEASURED = ("batch", "this", "find_many", "collect_many", "find_k_many")
+MEASURED = ("batch", "this", "find_many", "collect_many", "find_k_many", "find_k", "find")
 STATS = ("launches", "fused", "fallback", "overflow", "tasks_total", "tasks", "total",
-         "max_answer")
+         "max_answer", "find_launches", "find_tasks_total", "answer", "answer_k")
 
 
 def load(raw):
