@@ -26,6 +26,7 @@ HM_ERR_NOMEM = -4
 HM_ERR_RCCL = -5
 HM_ERR_INTERNAL = -6
 HM_ERR_TIMEOUT = -7
+HM_ERR_CANCELLED = -8
 
 HM_KIND_NONE, HM_KIND_GENERIC, HM_KIND_TILED, HM_KIND_CHAINED, HM_KIND_FUSED = 0, 1, 2, 3, 4
 HM_OPT_FORCE_GENERIC, HM_OPT_MERGE_RCCL, HM_OPT_GRID_PER_CU, HM_OPT_STREAMS = 1, 2, 3, 4
@@ -52,6 +53,15 @@ class HipMinerError(RuntimeError):
         self.rc = rc
         msg = strerror(rc) if _lib_or_none() else f"rc={rc}"
         super().__init__(f"{what}: {msg} (rc={rc})" if what else f"{msg} (rc={rc})")
+
+
+class HipMinerCancelled(HipMinerError):
+    """A find, find_k, find_many or find_k_many that Context.cancel stopped
+    (rc = HM_ERR_CANCELLED): nothing was written and the context is usable."""
+
+
+def _error(rc: int, what: str) -> HipMinerError:
+    return (HipMinerCancelled if rc == HM_ERR_CANCELLED else HipMinerError)(rc, what)
 
 
 class hm_result(ctypes.Structure):
@@ -136,6 +146,17 @@ class hm_find_k_many_stats(_Stats):
                 ("fused", ctypes.c_int32), ("fallback", ctypes.c_int32),
                 ("overflow", ctypes.c_int32), ("launches", ctypes.c_int32),
                 ("ndev", ctypes.c_int32)]
+
+
+class hm_cancel_stats(_Stats):
+    """hm_cancel_stats of include/hipminer.h (ABI 1.18)."""
+    _fields_ = [("latency_ms", ctypes.c_double), ("cancels", ctypes.c_uint64),
+                ("cancelled_calls", ctypes.c_uint64), ("launches_in_flight", ctypes.c_int32),
+                ("family", ctypes.c_int32)]
+
+
+HM_CANCEL_FAMILY_NONE, HM_CANCEL_FAMILY_FIND, HM_CANCEL_FAMILY_FIND_K = 0, 1, 2
+HM_CANCEL_FAMILY_FIND_MANY, HM_CANCEL_FAMILY_FIND_K_MANY = 3, 4
 
 
 class hm_collect_stats(_Stats):
@@ -230,6 +251,7 @@ def _prototypes() -> dict:
         "hm_find_k_cpu": (i, rng + [u64, sz, i, res, szp]),
         "hm_find_k_many": (i, [ctx, P(hm_find_k_request), i, res, szp]),
         "hm_find_k_many_cpu": (i, [P(hm_find_k_request), i, i, res, szp]),
+        "hm_cancel": (i, [ctx]),
         "hm_collect": (i, [ctx] + rng + [u64, res, sz, u64p]),
         "hm_collect_cpu": (i, rng + [u64, i, res, sz, u64p]),
         "hm_collect_many": (i, [ctx, P(hm_collect_request), i, u64p, res, sz, u64p]),
@@ -244,10 +266,11 @@ def _prototypes() -> dict:
         "hm_debug_auto_deadline_ms": (dbl, rng + [i]),
         "hm_debug_streams_made": (i, [ctx, i]),
         "hm_debug_plan": (i, rng + [i, P(i64), i]),
+        "hm_debug_no_relay": (i, [ctx, i]),
     }
     for cls in (hm_stats, hm_find_stats, hm_find_many_stats, hm_find_k_stats,
                 hm_find_k_many_stats, hm_collect_stats, hm_collect_many_stats, hm_verify_stats,
-                hm_verify_many_stats):
+                hm_verify_many_stats, hm_cancel_stats):
         family = "scan" if cls is hm_stats else cls.__name__[3:-6]
         table[f"hm_{family}_stats_sized"] = (i, [ctx, P(cls), sz])
     return table
@@ -366,8 +389,28 @@ class Context:
         rc = self._lib.hm_find(self._h, m, len(m), lo, hi, target, ctypes.byref(out),
                                ctypes.byref(found))
         if rc != HM_OK:
-            raise HipMinerError(rc, "hm_find")
+            raise _error(rc, "hm_find")
         return (int(out.hash), int(out.nonce)) if found.value else None
+
+    def cancel(self) -> bool:
+        """hm_cancel (ABI 1.18): stop the find, find_k, find_many or
+        find_k_many that another thread has in flight on this context.  True:
+        such a call was in flight and is signalled -- it raises
+        HipMinerCancelled, or returns its exact answer if that was already in
+        hand.  False: nothing cancellable was in flight, and nothing is
+        remembered (a later call is not affected).  ctypes releases the GIL
+        for the duration of a foreign call, so a Python thread can call this
+        while another is inside find(); it takes no lock and returns at once."""
+        rc = self._lib.hm_cancel(self._h)
+        if rc < 0:
+            raise HipMinerError(rc, "hm_cancel")
+        return rc == 1
+
+    def cancel_stats(self) -> dict:
+        """hm_cancel_stats_sized: cancels and cancelled calls since the context
+        was opened; latency_ms, launches_in_flight and family of the last
+        cancelled call."""
+        return self._stats("hm_cancel_stats_sized", hm_cancel_stats)
 
     def find_stats(self) -> dict:
         """hm_find_stats_sized: work accounting of the last find on this context."""
@@ -481,6 +524,13 @@ class Context:
         device_index-th device (debug export; ABI 1.8 makes them on first use)."""
         return int(self._lib.hm_debug_streams_made(self._h, device_index))
 
+    def debug_no_relay(self, on: bool) -> None:
+        """hm_debug_no_relay (test hook): no relay wave and no host test of the
+        cancel flag, so a call that cancel() signalled runs to its end."""
+        rc = self._lib.hm_debug_no_relay(self._h, int(on))
+        if rc != HM_OK:
+            raise HipMinerError(rc, "hm_debug_no_relay")
+
     def set_option(self, opt: int, value: int) -> None:
         rc = self._lib.hm_set_option(self._h, opt, value)
         if rc != HM_OK:
@@ -559,7 +609,7 @@ def _find_many(call, what: str, requests):
     rc = call(arr, n, outs, found)
     del keep
     if rc != HM_OK:
-        raise HipMinerError(rc, what)
+        raise _error(rc, what)
     return [(int(outs[i].hash), int(outs[i].nonce)) if found[i] else None for i in range(n)]
 
 
@@ -577,7 +627,7 @@ def _find_k(call, what: str, msg, k: int):
     n = ctypes.c_size_t(0)
     rc = call(m, buf, ctypes.byref(n))
     if rc != HM_OK:
-        raise HipMinerError(rc, what)
+        raise _error(rc, what)
     t = int(n.value)
     if t == 0:
         return []
@@ -607,7 +657,7 @@ def _find_k_many(call, what: str, requests):
     rc = call(arr, n, buf, counts)
     del keep
     if rc != HM_OK:
-        raise HipMinerError(rc, what)
+        raise _error(rc, what)
     out, off = [], 0
     for i in range(n):
         c = int(counts[i])

@@ -32,7 +32,9 @@
 //   fused_find_k_kernels.hip per request, hm_find_k's path for what is left.
 //   The three *_many calls above share one chunk runner on the host
 //   (batch.cpp); fused_tasks.hpp has the fused batch kernels' task walker
-//   (hm_fused_find_kernel runs on it).  hm_find and hm_find_k share one
+//   (hm_fused_find_kernel runs on it).  hm_cancel (ABI 1.18): cancel.hpp, the
+//   flag's state machine; cancel_relay.hpp, the relay wave of the four
+//   find-family kernel files.  hm_find and hm_find_k share one
 //   early-exit walk (find_walk), every family's stats getter is stats_out over
 //   its StatsSlot of hm_ctx (both hm_internal.hpp), and guarded() and the
 //   null-message rule (msg_or_empty) are plan.hpp's, shared with host_scan.cpp.
@@ -73,7 +75,8 @@ uint64_t hm_hash(const uint8_t* msg, size_t len, uint64_t nonce) {
 // 1.15: hm_collect_many, hm_collect_many_cpu, hm_collect_many_stats_sized, HM_OPT_COLLECT_WINDOW
 // 1.16: hm_find_k, hm_find_k_cpu, hm_find_k_stats_sized, HM_OPT_FIND_K_BUF
 // 1.17: hm_find_k_many, hm_find_k_many_cpu, hm_find_k_many_stats_sized
-int hm_version(void) { return (1 << 16) | 17; }
+// 1.18: hm_cancel, HM_ERR_CANCELLED, hm_cancel_stats_sized; debug export hm_debug_no_relay
+int hm_version(void) { return (1 << 16) | 18; }
 
 // The digest of the sources this library was built from (build_id.py), kept
 // in the binary behind a tag so tools can read it without loading the library.
@@ -106,6 +109,9 @@ const char* hm_strerror(int rc) {
         case HM_ERR_TIMEOUT:
             return "GPU scan missed its deadline (HM_OPT_DEADLINE_MS); the context is "
                    "abandoned: close it, open a new one or scan on the host";
+        case HM_ERR_CANCELLED:
+            return "the call was stopped by hm_cancel; nothing was written and the context is "
+                   "usable";
         default: return "unknown error";
     }
 }
@@ -123,8 +129,10 @@ void hm_close(hm_ctx* ctx) {
         // an abandoned context (HM_ERR_TIMEOUT) may still have work running:
         // its streams, buffers and pinned readback slot are left to the
         // process exit rather than waited for
-        if (!ctx->abandoned)
+        if (!ctx->abandoned) {
             for (auto& dv : ctx->devs) device_free(dv);
+            cancel_flag_free(ctx);
+        }
     }
     delete ctx;
 }
@@ -337,6 +345,20 @@ int hm_find_k_many_stats_sized(const hm_ctx* ctx, hm_find_k_many_stats* out, siz
     return stats_out(ctx, &hm_ctx::find_k_many_stats, out, size, HM_FIND_K_MANY_STATS_SIZE_1_17);
 }
 
+// hm_cancel: no ctx->mu, no HIP call (cancel.hpp).  An abandoned context has no call in
+// flight, so it answers 0.
+int hm_cancel(hm_ctx* ctx) {
+    if (!ctx) return HM_ERR_INVALID;
+    return ctx->cancel.request();
+}
+
+int hm_cancel_stats_sized(const hm_ctx* ctx, hm_cancel_stats* out, size_t size) {
+    if (!ctx || !out || size < HM_CANCEL_STATS_SIZE_1_18) return HM_ERR_INVALID;
+    const hm_cancel_stats st = const_cast<hm_ctx*>(ctx)->cancel.read();
+    memcpy(out, &st, std::min(size, sizeof st));
+    return HM_OK;
+}
+
 int hm_collect(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
                uint64_t target, hm_result* out, size_t cap, uint64_t* total) {
     if (!ctx || !total || (!msg && len) || cap > HM_COLLECT_CAP_MAX || (cap && !out))
@@ -477,6 +499,15 @@ int hm_debug_streams_made(const hm_ctx* ctx, int i) {
     if (!ctx || i < 0 || i >= (int)ctx->devs.size()) return -1;
     std::lock_guard<std::mutex> g(ctx->mu);
     return ctx->devs[i].nmade;
+}
+
+// hm_cancel's test hook: no relay wave and no host test of the flag (hm_internal.hpp
+// cancel_ptr, cancel_seen), so a signalled call runs to its end.
+int hm_debug_no_relay(hm_ctx* ctx, int on) {
+    if (!ctx) return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    ctx->no_relay = on != 0;
+    return HM_OK;
 }
 
 // Writes up to `cap` segment descriptors as 13 x int64:

@@ -124,6 +124,28 @@ void device_free(Device& dv) {
     dv.ordinal = -1;
 }
 
+// hm_cancel's flag: one word (a cache line of its own) of pinned host memory,
+// mapped into every device and coherent, like dv.host_out; each device gets its
+// own pointer to it.  The host writes it (cancel.hpp), a find launch's relay wave
+// reads it (cancel_relay.hpp).
+static int cancel_flag_init(hm_ctx* ctx) {
+    HIPCHK(hipSetDevice(ctx->devs[0].ordinal));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->cancel.flag), 64,
+                         hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent));
+    *ctx->cancel.flag = 0;
+    for (Device& dv : ctx->devs) {
+        HIPCHK(hipSetDevice(dv.ordinal));
+        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&dv.cancel_dev), ctx->cancel.flag,
+                                       0));
+    }
+    return HM_OK;
+}
+
+void cancel_flag_free(hm_ctx* ctx) {
+    if (ctx->cancel.flag) (void)hipHostFree(ctx->cancel.flag);
+    ctx->cancel.flag = nullptr;
+}
+
 int open_devices(const int* devices, int ndev, hm_ctx** out) {
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return HM_ERR_NO_DEVICE;
@@ -142,11 +164,13 @@ int open_devices(const int* devices, int ndev, hm_ctx** out) {
     try {
         ctx->devs.resize(ords.size());
         for (size_t i = 0; i < ords.size() && rc == HM_OK; ++i) rc = device_init(ctx->devs[i], ords[i]);
+        if (rc == HM_OK) rc = cancel_flag_init(ctx);
     } catch (const std::bad_alloc&) {
         rc = HM_ERR_NOMEM;
     }
     if (rc) {
         for (auto& dv : ctx->devs) device_free(dv);
+        cancel_flag_free(ctx);
         delete ctx;
         return rc;
     }

@@ -30,6 +30,14 @@
 // A hit at nonce MaxUint64 cannot be told from "none" in the stop word, so
 // the kernels never publish it and the host tests that one nonce itself.
 //
+// hm_cancel (ABI 1.18, cancel.hpp): the call is cancellable from its opening to
+// its return (CancelScope).  The walk tests the context's cancel flag before it
+// issues each launch and after each wait and readback, before it looks at the
+// words it read -- a launch's relay wave lowers the stop word to 0 once the flag
+// is set, and that word is no hit (cancel_relay.hpp has the invariant).  On
+// observation the streams are drained (every launch still queued exits on its
+// first read of the word) and the call returns HM_ERR_CANCELLED.
+//
 // The walk itself -- find_walk over FindDev, find_next_step, find_issue
 // (hm_internal.hpp) and find_collect -- is shared with hm_find_k (find_k.cpp),
 // which runs it over its own kernels, trailer and control words.
@@ -110,6 +118,7 @@ int find_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_t 
                                fa.tasks_run = dv.find_ctl + 1;
                                fa.target = target;
                                fa.launch_lo = launch_lo;
+                               fa.cancel = cancel_ptr(ctx, dv);
                                return fa;
                            });
         if (rc) return rc;
@@ -139,11 +148,12 @@ int find_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64
     size_t mlen;
     int rc = begin_ranged_call(ctx, msg, len, lo, hi, t0, &m, &mlen);
     if (rc) return rc;
+    CancelScope cancel(ctx, HM_CANCEL_FAMILY_FIND);
     FindTally tally;
     hm_result res;
     int hit = 0;
     rc = find_core(ctx, m, mlen, lo, hi, target, &tally, &res, &hit);
-    if (rc) return rc;
+    if (rc) return cancel.end(rc);
     hm_find_stats st{};
     st.kernel_ms = tally.kernel_ms;
     st.nonces_enqueued = tally.nonces;

@@ -25,6 +25,11 @@
 // ascending windows of that range: each sized from target / 2^64 and the hits
 // still missing, halved when its total exceeds its cap, until k hits are in
 // hand or the range is done.
+//
+// hm_cancel (ABI 1.18): as hm_find (find.cpp) -- the walk tests the cancel flag
+// before each launch and after each readback, before the control words count
+// for anything (a relay wave's stop = 0 is not "k records at or below 0"); the
+// overflow path tests it between windows.
 // ---------------------------------------------------------------------------
 #include "hm_internal.hpp"
 
@@ -41,6 +46,9 @@ int find_k_windows(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint
     uint64_t span = 0;  // the next window's nonces; 0: size it from p
     std::vector<hm_result> win;
     for (;;) {
+        // hm_cancel: the collect kernels have no relay, so the flag is tested between windows
+        // (the last one has ended: nothing is in flight)
+        if (cancel_seen(ctx)) return cancel_observed(ctx, 0);
         if (span == 0) {
             // about 16 hits more than are missing, so one window usually ends the call
             const double want = ((double)(k - recs->size()) + 16.0) / p;
@@ -104,6 +112,7 @@ int find_k_core(hm_ctx* ctx, const uint8_t* m, size_t mlen, uint64_t lo, uint64_
                            ka.launch_lo = launch_lo;
                            ka.cap = (uint32_t)B;
                            ka.k = (uint32_t)k;
+                           ka.cancel = cancel_ptr(ctx, dv);
                            return ka;
                        });
         if (rc) return rc;
@@ -151,9 +160,10 @@ int find_k_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint
     size_t mlen;
     int rc = begin_ranged_call(ctx, msg, len, lo, hi, t0, &m, &mlen);
     if (rc) return rc;
+    CancelScope cancel(ctx, HM_CANCEL_FAMILY_FIND_K);
     FindKTally kt;
     rc = find_k_core(ctx, m, mlen, lo, hi, target, k, &kt, recs);
-    if (rc) return rc;
+    if (rc) return cancel.end(rc);
     const FindTally& tally = kt.t;
     hm_find_k_stats st{};
     st.kernel_ms = tally.kernel_ms;

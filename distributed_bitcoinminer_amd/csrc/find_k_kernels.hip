@@ -36,6 +36,21 @@
 // No wave waits on another beyond the dispenser's existing LDS hand-off, and
 // nothing here spins.
 //
+// hm_cancel (ABI 1.18; cancel_relay.hpp).  Wave 0 of workgroup 0
+// is the launch's RELAY: at kernel entry and between its tasks (right after each
+// task it ran, so before the next one it takes; the generic kernel: before each
+// step) it reads the context's cancel flag (FindKArgs::cancel, pinned host memory;
+// one relaxed system-scope load) and, if it is set, lowers the stop word to 0,
+// from where
+// skip / leave / exit above end this launch and those queued behind it.  A
+// word lowered so is FORGED -- 0 is not a hit, nor "k records at or below 0" -- and the invariants
+// below speak of a call that was not cancelled.  The cancel invariant:
+//   The word is forged only if the flag is set.  The flag is set before the
+//   device can see it, and only the call's own thread clears it (at call
+//   start).  Therefore the host, which tests the flag after every wait or
+//   readback and BEFORE it interprets any control word, never mistakes a
+//   forged word for an answer.
+//
 // The answer is exact whatever the dispatch order, because
 //   1. a record is written only for an in-range, below-target, non-surplus
 //      lane (take_step(WaveFirstK&), as WaveCollect's),
@@ -56,6 +71,7 @@
 // seg_walk.cpp).
 #include <hip/hip_runtime.h>
 
+#include "cancel_relay.hpp"
 #include "kernels.hpp"
 #include "scan_tasks.hpp"
 #include "sha256_defs.hpp"
@@ -107,6 +123,8 @@ __global__ void HM_TILED_BOUNDS hm_find_k_tiled_kernel(const FindKTiledArgs KA) 
     __shared__ LdsQueue queue;
     lds_queue_init(&queue);
     uint32_t ran = 0;
+    const bool relay = cancel_is_relay(F.cancel);
+    cancel_relay(relay, F.cancel, F.ctl + kFkStop);
     if (find_k_stop(F) < F.launch_lo) return;
 
     for (;;) {
@@ -125,6 +143,7 @@ __global__ void HM_TILED_BOUNDS hm_find_k_tiled_kernel(const FindKTiledArgs KA) 
             A.seg_hi, A.vmax, A.q, A.lane_shift, A.loop_shift, A.s0_loop, A.trailer_kw, fk, sums);
         ++ran;
         if (fk.c) find_k_publish(F, fk.c, fk.mx);
+        cancel_relay(relay, F.cancel, F.ctl + kFkStop);
     }
     find_k_count(F, ran);
 }
@@ -138,6 +157,8 @@ __global__ void __launch_bounds__(kBlock) hm_find_k_chained_kernel(const FindKCh
     __shared__ LdsQueue queue;
     lds_queue_init(&queue);
     uint32_t ran = 0;
+    const bool relay = cancel_is_relay(F.cancel);
+    cancel_relay(relay, F.cancel, F.ctl + kFkStop);
     if (find_k_stop(F) < F.launch_lo) return;
 
     for (;;) {
@@ -155,6 +176,7 @@ __global__ void __launch_bounds__(kBlock) hm_find_k_chained_kernel(const FindKCh
                             tile_base, A.pow10f, A.seg_lo, A.seg_hi, A.vmax, A.q, A.kwt, fk, sums);
         ++ran;
         if (fk.c) find_k_publish(F, fk.c, fk.mx);
+        cancel_relay(relay, F.cancel, F.ctl + kFkStop);
     }
     find_k_count(F, ran);
 }
@@ -170,9 +192,12 @@ __global__ void __launch_bounds__(kBlock) hm_find_k_generic_kernel(const FindKGe
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     const uint32_t lane = __lane_id();
     uint32_t ran = 0;
+    const bool relay = cancel_is_relay(F.cancel);
+    cancel_relay(relay, F.cancel, F.ctl + kFkStop);
     if (find_k_stop(F) < F.launch_lo) return;
     for (uint64_t kb = (uint64_t)blockIdx.x * blockDim.x + uni(threadIdx.x / kWaveSize) * kWaveSize;
          kb <= A.count_m1;) {
+        cancel_relay(relay, F.cancel, F.ctl + kFkStop);
         if (A.seg_lo + kb > find_k_stop(F)) break;
         // lanes past the segment's end repeat the step's first nonce: surplus
         const bool live = A.count_m1 - kb >= lane;

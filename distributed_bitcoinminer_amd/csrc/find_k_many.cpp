@@ -38,6 +38,11 @@
 //                                 request goes down find_k_core
 // find_k_core is hm_find_k's per-segment path (find_k.cpp), one request after
 // another on stream 0.
+//
+// hm_cancel (ABI 1.18): as hm_find_many (find_many.cpp) -- each fused launch's
+// relay wave ends it, the host tests the cancel flag after the chunk's wait and
+// readback, before any control word or record is looked at, and find_k_core
+// tests it before each leftover's first launch and between overflow windows.
 // ---------------------------------------------------------------------------
 #include "hm_internal.hpp"
 
@@ -109,10 +114,13 @@ int find_k_chunk(hm_ctx* ctx, const hm_find_k_request* reqs, int n, int index0,
             ka->f.launch_lo = reqs[r].lo;
             ka->f.cap = (uint32_t)sl[r].B;
             ka->f.k = (uint32_t)reqs[r].k;
+            ka->f.cancel = cancel_ptr(ctx, dv);
             return (int)HM_OK;
         });
     if (!rc) rc = C.finish(&Device::find_k_many_ctl, (size_t)kFkWords * n, &fused);
     if (rc) return rc;
+    // hm_cancel: after the wait and the readback, before any word is looked at
+    if (cancel_seen(ctx)) return cancel_observed(ctx, fused.launches);
     st->nonces_enqueued += fused.nonces;
     st->tasks_total += fused.tasks;
     st->launches += fused.launches;
@@ -185,6 +193,7 @@ int find_k_many_locked(hm_ctx* ctx, const hm_find_k_request* reqs, int n,
     const auto t0 = std::chrono::steady_clock::now();
     int rc = batch_open(ctx, reqs, n, t0);
     if (rc) return rc;
+    CancelScope cancel(ctx, HM_CANCEL_FAMILY_FIND_K_MANY);
     hm_find_k_many_stats st{};
     recs->assign((size_t)n, {});
     const int ndev = (int)ctx->devs.size();
@@ -199,8 +208,10 @@ int find_k_many_locked(hm_ctx* ctx, const hm_find_k_request* reqs, int n,
             s += B;
             ++m;
         }
-        rc = find_k_chunk(ctx, reqs + c, m, c, recs->data() + c, &st);
-        if (rc) return drain_streams(ctx, rc);
+        // hm_cancel: nothing is in flight between chunks
+        rc = cancel_seen(ctx) ? cancel_observed(ctx, 0)
+                              : find_k_chunk(ctx, reqs + c, m, c, recs->data() + c, &st);
+        if (rc) return cancel.end(drain_streams(ctx, rc));
         c += m;
     }
     for (int r = 0; r < n; ++r) st.found += (*recs)[r].size();

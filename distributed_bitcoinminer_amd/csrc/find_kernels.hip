@@ -29,6 +29,21 @@
 //   count    each wave adds the tasks it ran to FindArgs::tasks_run once
 // No wave waits on another beyond the dispenser's existing LDS hand-off.
 //
+// hm_cancel (ABI 1.18; cancel_relay.hpp).  Wave 0 of workgroup 0
+// is the launch's RELAY: at kernel entry and between its tasks (right after each
+// task it ran, so before the next one it takes; the generic kernel: before each
+// step) it reads the context's cancel flag (FindArgs::cancel, pinned host memory;
+// one relaxed system-scope load) and, if it is set, lowers the stop word to 0,
+// from where
+// skip / leave / exit above end this launch and those queued behind it.  A
+// word lowered so is FORGED -- 0 is not a hit -- and the invariants
+// below speak of a call that was not cancelled.  The cancel invariant:
+//   The word is forged only if the flag is set.  The flag is set before the
+//   device can see it, and only the call's own thread clears it (at call
+//   start).  Therefore the host, which tests the flag after every wait or
+//   readback and BEFORE it interprets any control word, never mistakes a
+//   forged word for an answer.
+//
 // The final word is the lowest hit whatever the dispatch order, because
 //   1. only nonces n in [seg_lo, seg_hi] with Hash(msg, n) < target are
 //      published (take_step(WaveFirst&)),
@@ -43,6 +58,7 @@
 // seg_walk.cpp).
 #include <hip/hip_runtime.h>
 
+#include "cancel_relay.hpp"
 #include "kernels.hpp"
 #include "scan_tasks.hpp"
 #include "sha256_defs.hpp"
@@ -93,6 +109,8 @@ __global__ void HM_TILED_BOUNDS hm_find_tiled_kernel(const FindTiledArgs FA) {
     __shared__ LdsQueue queue;
     lds_queue_init(&queue);
     uint32_t ran = 0;
+    const bool relay = cancel_is_relay(F.cancel);
+    cancel_relay(relay, F.cancel, F.word);
     if (find_stop(F) < F.launch_lo) return;
 
     for (;;) {
@@ -110,6 +128,7 @@ __global__ void HM_TILED_BOUNDS hm_find_tiled_kernel(const FindTiledArgs FA) {
             A.seg_hi, A.vmax, A.q, A.lane_shift, A.loop_shift, A.s0_loop, A.trailer_kw, first, sums);
         ++ran;
         if (first.nonce < before) find_publish(F, first.nonce);
+        cancel_relay(relay, F.cancel, F.word);
     }
     find_count(F, ran);
 }
@@ -123,6 +142,8 @@ __global__ void __launch_bounds__(kBlock) hm_find_chained_kernel(const FindChain
     __shared__ LdsQueue queue;
     lds_queue_init(&queue);
     uint32_t ran = 0;
+    const bool relay = cancel_is_relay(F.cancel);
+    cancel_relay(relay, F.cancel, F.word);
     if (find_stop(F) < F.launch_lo) return;
 
     for (;;) {
@@ -140,6 +161,7 @@ __global__ void __launch_bounds__(kBlock) hm_find_chained_kernel(const FindChain
                             sums);
         ++ran;
         if (first.nonce < before) find_publish(F, first.nonce);
+        cancel_relay(relay, F.cancel, F.word);
     }
     find_count(F, ran);
 }
@@ -154,9 +176,12 @@ __global__ void __launch_bounds__(kBlock) hm_find_generic_kernel(const FindGener
     const uint32_t lane = __lane_id();
     uint32_t ran = 0;
     uint64_t best = ~0ull;  // wave-uniform
+    const bool relay = cancel_is_relay(F.cancel);
+    cancel_relay(relay, F.cancel, F.word);
     if (find_stop(F) < F.launch_lo) return;
     for (uint64_t kb = (uint64_t)blockIdx.x * blockDim.x + uni(threadIdx.x / kWaveSize) * kWaveSize;
          kb <= A.count_m1;) {
+        cancel_relay(relay, F.cancel, F.word);
         const uint64_t stop = find_stop(F);
         if (A.seg_lo + kb > stop) break;
         if (stop < best) best = stop;

@@ -20,6 +20,12 @@
 //             HM_OPT_FUSED = 0 sends every request there.
 // A hit at nonce MaxUint64 cannot be told from "none" in the stop word: the
 // kernel never publishes it and the host tests that one nonce itself.
+//
+// hm_cancel (ABI 1.18): every fused launch has a relay wave (the planner
+// re-seeds each request's word, each launch's relay lowers it again), so a
+// signalled chunk ends by itself; the host tests the cancel flag after the
+// chunk's wait and readback, before any word is looked at, and find_core tests
+// it before each leftover's first launch (find_walk).
 // ---------------------------------------------------------------------------
 #include "hm_internal.hpp"
 
@@ -47,10 +53,13 @@ int find_chunk(hm_ctx* ctx, const hm_find_request* reqs, int n, int index0, hm_r
             ka->f.tasks_run = dv.find_many_ctl + 2 * r + 1;
             ka->f.target = reqs[r].target;
             ka->f.launch_lo = reqs[r].lo;
+            ka->f.cancel = cancel_ptr(ctx, dv);
             return HM_OK;
         });
     if (!rc) rc = C.finish(&Device::find_many_ctl, (size_t)2 * n, &fused);
     if (rc) return rc;
+    // hm_cancel: after the wait and the readback, before any word is looked at
+    if (cancel_seen(ctx)) return cancel_observed(ctx, fused.launches);
     st->nonces_enqueued += fused.nonces;
     st->tasks_total += fused.tasks;
     st->launches += fused.launches;
@@ -98,11 +107,14 @@ int find_many_locked(hm_ctx* ctx, const hm_find_request* reqs, int n, hm_result*
     const auto t0 = std::chrono::steady_clock::now();
     int rc = batch_open(ctx, reqs, n, t0);
     if (rc) return rc;
+    CancelScope cancel(ctx, HM_CANCEL_FAMILY_FIND_MANY);
     hm_find_many_stats st{};
     for (int c = 0; c < n; c += kMaxBatch) {
         const int m = std::min(kMaxBatch, n - c);
-        rc = find_chunk(ctx, reqs + c, m, c, outs + c, found + c, &st);
-        if (rc) return drain_streams(ctx, rc);
+        // hm_cancel: nothing is in flight between chunks
+        rc = cancel_seen(ctx) ? cancel_observed(ctx, 0)
+                              : find_chunk(ctx, reqs + c, m, c, outs + c, found + c, &st);
+        if (rc) return cancel.end(drain_streams(ctx, rc));
     }
     for (int r = 0; r < n; ++r) st.found += found[r];
     st.requests = n;

@@ -47,6 +47,19 @@
 //   count    each wave adds the tasks it ran to tasks_run once
 // Nothing spins and no wave waits on another.
 //
+// hm_cancel (ABI 1.18; cancel_relay.hpp).  Wave 0 of workgroup 0
+// is the launch's RELAY: at kernel entry and before each task it takes it reads
+// the context's cancel flag (FindKArgs::cancel, pinned host memory; one relaxed
+// system-scope load) and, if it is set, lowers the stop word to 0, from where
+// skip / leave / exit above end this launch and those queued behind it.  A
+// word lowered so is FORGED -- 0 is not a hit, nor "k records at or below 0" -- and the invariants
+// below speak of a call that was not cancelled.  The cancel invariant:
+//   The word is forged only if the flag is set.  The flag is set before the
+//   device can see it, and only the call's own thread clears it (at call
+//   start).  Therefore the host, which tests the flag after every wait or
+//   readback and BEFORE it interprets any control word, never mistakes a
+//   forged word for an answer.
+//
 // A task's smallest nonce (task_lo) is lane 0's first loop value, as in
 // fused_find_kernels.hip; it may be lower than the task's smallest IN-RANGE
 // nonce, never higher.  The skip test is min(task_lo, seg_hi) > stop.  The
@@ -99,6 +112,7 @@
 // seg_walk.cpp).
 #include <hip/hip_runtime.h>
 
+#include "cancel_relay.hpp"
 #include "kernels.hpp"
 #include "scan_tasks.hpp"
 #include "sha256_defs.hpp"
@@ -115,6 +129,8 @@ typedef const __attribute__((address_space(4))) FusedArgs FusedArgsK;
 // The request's control words and its wave-side state.
 struct FindKWave {
     uint64_t* ctl;
+    const uint32_t* cancel;  // hm_cancel: the flag, and whether this wave relays it
+    bool relay;
     WaveFirstK fk;
     uint32_t ran = 0;
 };
@@ -122,6 +138,7 @@ struct FindKWave {
 // Before a task whose smallest nonce is task_lo: false = skip it (and leave).
 // Otherwise the task's c and mx start at 0.
 DEV bool fk_enter(FindKWave& w, uint64_t task_lo, uint64_t seg_hi) {
+    cancel_relay(w.relay, w.cancel, w.ctl + kFkStop);
     uint64_t stop = 0;
     if (__lane_id() == 0)
         stop = __hip_atomic_load(w.ctl + kFkStop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -257,6 +274,8 @@ __global__ void __launch_bounds__(kBlock) hm_fused_find_k_kernel(const FusedFind
     const uint32_t wslot = blockIdx.x * (kBlock / kWaveSize) + uni(threadIdx.x / kWaveSize);
     FindKWave w;
     w.ctl = P->f.ctl;
+    w.cancel = P->f.cancel;
+    w.relay = cancel_is_relay(w.cancel);
     w.fk.target = P->f.target;
     w.fk.thi = (uint32_t)((P->f.target - 1) >> 32);
     w.fk.cursor = P->f.ctl + kFkCursor;

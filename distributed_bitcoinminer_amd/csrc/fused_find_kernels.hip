@@ -35,6 +35,19 @@
 //   count    each wave adds the tasks it ran to FindArgs::tasks_run once
 // Nothing spins and no wave waits on another.
 //
+// hm_cancel (ABI 1.18; cancel_relay.hpp).  Wave 0 of workgroup 0
+// is the launch's RELAY: at kernel entry and before each task it takes it reads
+// the context's cancel flag (FindArgs::cancel, pinned host memory; one relaxed
+// system-scope load) and, if it is set, lowers the stop word to 0, from where
+// skip / leave / exit above end this launch and those queued behind it.  A
+// word lowered so is FORGED -- 0 is not a hit -- and the invariants
+// below speak of a call that was not cancelled.  The cancel invariant:
+//   The word is forged only if the flag is set.  The flag is set before the
+//   device can see it, and only the call's own thread clears it (at call
+//   start).  Therefore the host, which tests the flag after every wait or
+//   readback and BEFORE it interprets any control word, never mistakes a
+//   forged word for an answer.
+//
 // A task's smallest nonce (task_lo) is lane 0's first loop value:
 //   tiled    tile_base + chunk * 6400 + t1 * 10 + t0b
 //   chained  tile_base + chunk * 64 * 10^f + tb
@@ -71,6 +84,7 @@
 // seg_walk.cpp).
 #include <hip/hip_runtime.h>
 
+#include "cancel_relay.hpp"
 #include "fused_tasks.hpp"
 #include "kernels.hpp"
 #include "scan_tasks.hpp"
@@ -87,6 +101,7 @@ typedef const __attribute__((address_space(4))) FusedFindArgs FusedFindArgsK;
 // The request's stop word and its wave-side state: fused_walk's policy.
 struct FindWave {
     uint64_t* word;
+    bool relay;  // hm_cancel: this wave relays the flag (FindArgs::cancel, read from the kernarg)
     WaveFirst first;
     uint64_t before;  // the bound the current task started from
     uint32_t ran = 0;
@@ -96,6 +111,9 @@ struct FindWave {
     // end): false = skip it (and leave).  Otherwise the wave's bound drops to
     // the published hit.
     DEV bool enter(uint64_t task_lo, uint64_t seg_hi) {
+        if (relay)
+            cancel_relay(true, ((FusedFindArgsK*)__builtin_amdgcn_kernarg_segment_ptr())->f.cancel,
+                         word);
         uint64_t stop = 0;
         if (__lane_id() == 0)
             stop = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -119,6 +137,7 @@ __global__ void __launch_bounds__(kBlock) hm_fused_find_kernel(const FusedFindAr
     FusedFindArgsK* P = (FusedFindArgsK*)__builtin_amdgcn_kernarg_segment_ptr();
     FindWave w;
     w.word = P->f.word;
+    w.relay = cancel_is_relay(P->f.cancel);
     w.first.target = P->f.target;
     w.first.thi = (uint32_t)((P->f.target - 1) >> 32);
     fused_walk(&P->a, w);

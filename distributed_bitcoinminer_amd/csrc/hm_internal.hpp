@@ -37,6 +37,7 @@
 
 #include "../../include/hipminer.h"
 #include "../../include/hipminer_debug.h"
+#include "cancel.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
 
@@ -148,6 +149,8 @@ struct Device {
     uint64_t* vm_refs = nullptr;
     size_t vm_refs_cap = 0;
     hm_result* host_out = nullptr; // pinned, fine-grained [kMaxBatch]: the 16-B readback slots
+    // hm_cancel: this device's pointer to the context's cancel flag (hm_ctx::cancel.flag)
+    uint32_t* cancel_dev = nullptr;
     hipEvent_t join[kStreams] = {};
     hipEvent_t gate = nullptr;     // stream 0 reached its last dominant segment
     hipEvent_t t0 = nullptr;       // timing origin of the current call
@@ -215,6 +218,10 @@ struct hm_ctx {
     std::chrono::steady_clock::time_point deadline_at{};
     double deadline_ms = 0;  // the current call's deadline (hm_stats.deadline_ms)
     bool abandoned = false;
+    // hm_cancel (cancel.hpp): the flag (pinned host memory, made at hm_open), cancel_mu, whether
+    // a cancellable call is in flight, the timestamp and the record.  Not guarded by `mu`.
+    hm::CancelState cancel;
+    bool no_relay = false;  // hm_debug_no_relay (test hook: cancel reaches neither GPU nor host)
     int merge = HM_MERGE_NONE;  // how the current call merged device results
     // every family keeps its own record: hm_find leaves the last scan's alone
     hm::StatsSlot<hm_stats> scan_stats;
@@ -260,6 +267,7 @@ inline int ctl_block(uint64_t** p, size_t words) {
 // ---- device.cpp ----
 int open_devices(const int* devices, int ndev, hm_ctx** out);
 void device_free(Device& dv);
+void cancel_flag_free(hm_ctx* ctx);  // hm_close, after every device_free
 bool distinct_ordinals(const hm_ctx* ctx);
 int next_event(Device& dv, hipEvent_t* ev);
 int make_streams(Device& dv, int n);
@@ -450,6 +458,37 @@ int begin_ranged_call(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, 
 // a scan.  Returns rc.
 int drain_failed(hm_ctx* ctx, int rc);
 
+// ---- hm_cancel: the call's side (cancel.hpp has the state machine and its rules) ----
+// A cancellable call -- hm_find, hm_find_k, hm_find_many, hm_find_k_many -- from just after its
+// opening (begin_ranged_call, batch_open) to its return, ctx->mu held: the flag is cleared and
+// the call is in flight for hm_cancel while the scope lives.  The call returns through end(rc);
+// a cancelled call whose drain missed the deadline is a timeout (the context is abandoned).
+struct CancelScope {
+    CancelScope(hm_ctx* ctx, int family) : ctx(ctx) { ctx->cancel.begin(family); }
+    ~CancelScope() { ctx->cancel.finish(rc); }
+    CancelScope(const CancelScope&) = delete;
+    CancelScope& operator=(const CancelScope&) = delete;
+    int end(int r) { return rc = r == HM_ERR_CANCELLED && ctx->abandoned ? HM_ERR_TIMEOUT : r; }
+
+private:
+    hm_ctx* ctx;
+    int rc = HM_OK;
+};
+// What a find-family launch gets as FindArgs::cancel / FindKArgs::cancel.
+inline const uint32_t* cancel_ptr(const hm_ctx* ctx, const Device& dv) {
+    return ctx->no_relay ? nullptr : dv.cancel_dev;
+}
+// The host's test of the flag: after every wait or readback and BEFORE any control word is
+// interpreted (a set flag means the words may be forged, cancel_relay.hpp), and before work is
+// issued.
+inline bool cancel_seen(const hm_ctx* ctx) { return !ctx->no_relay && ctx->cancel.seen(); }
+// The flag was seen with `inflight` launches queued or running: HM_ERR_CANCELLED, which the
+// caller returns through drain_failed / drain_streams.
+inline int cancel_observed(hm_ctx* ctx, int inflight) {
+    ctx->cancel.observed(inflight);
+    return HM_ERR_CANCELLED;
+}
+
 // ---- scan.cpp: the fused launch, shared with batch.cpp ----
 bool fusible(const std::vector<SegPlan>& segs);
 // The task order of a fused launch without an early exit: costliest layout
@@ -542,6 +581,13 @@ int find_walk(hm_ctx* ctx, const MsgPlan& mp, uint64_t lo, uint64_t hi, Family f
     *best = ~0ull;
     PieceWalk pieces(ctx, mp, lo, hi);
     std::vector<std::vector<SegPlan>> shards;
+    // hm_cancel: the flag is tested before each launch is issued and after each find_collect,
+    // before the control words it read are looked at (they may be forged)
+    auto in_flight = [&] {
+        int n = 0;
+        for (const FindDev& fd : fds) n += fd.inflight;
+        return n;
+    };
     // later pieces lie above a hit (hm_find_k: above every record written so far, the bound
     // among them)
     while (*best == ~0ull && pieces.next(&shards)) {
@@ -556,6 +602,8 @@ int find_walk(hm_ctx* ctx, const MsgPlan& mp, uint64_t lo, uint64_t hi, Family f
                 Device& dv = ctx->devs[i];
                 if (hipSetDevice(dv.ordinal) != hipSuccess) return drain_failed(ctx, HM_ERR_HIP);
                 while (fds[i].inflight < kFindLookahead) {
+                    if (cancel_seen(ctx))
+                        return drain_failed(ctx, cancel_observed(ctx, in_flight()));
                     bool issued = false;
                     int rc = find_issue(ctx, dv, fds[i], mp, family, *best, tally, &issued,
                                         [&](uint64_t launch_lo) { return make(dv, launch_lo); });
@@ -568,8 +616,10 @@ int find_walk(hm_ctx* ctx, const MsgPlan& mp, uint64_t lo, uint64_t hi, Family f
             for (int i = 0; i < ndev; ++i) {
                 if (!fds[i].inflight) continue;
                 Device& dv = ctx->devs[i];
+                const int waited_for = in_flight();
                 int rc = find_collect(ctx, dv, fds[i], tally, dv.*ctl, nwords);
                 if (rc) return drain_failed(ctx, rc);
+                if (cancel_seen(ctx)) return drain_failed(ctx, cancel_observed(ctx, waited_for));
                 *best = std::min(*best, fds[i].ctl[0]);
             }
         }

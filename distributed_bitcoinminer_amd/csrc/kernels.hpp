@@ -224,6 +224,9 @@ struct FindArgs {
     uint64_t* tasks_run;   // += tasks whose hash loop ran, once per wave at exit
     uint64_t target;       // >= 1
     uint64_t launch_lo;    // the launch's smallest nonce: word < launch_lo -> exit at once
+    // hm_cancel (cancel_relay.hpp): the device's pointer to the context's cancel
+    // flag, read by the launch's relay wave alone; null = no relay
+    const uint32_t* cancel;
 };
 struct FindTiledArgs {
     TiledArgs t;
@@ -309,6 +312,7 @@ struct FindKArgs {
     uint64_t launch_lo;  // the launch's smallest nonce: stop < launch_lo -> exit at once
     uint32_t cap;        // k <= cap <= HM_COLLECT_CAP_MAX
     uint32_t k;          // 1 .. HM_FIND_K_MAX
+    const uint32_t* cancel;  // as FindArgs::cancel
 };
 struct FindKTiledArgs {
     TiledArgs t;

@@ -43,7 +43,9 @@
  * Threading: calls on one context are serialised by an internal mutex; every
  * call re-binds its device (hipSetDevice), so Go may call from any OS thread.
  * hm_close must not race other calls on the same context (the caller owns
- * the context's lifetime, as with any C handle).
+ * the context's lifetime, as with any C handle).  hm_cancel (ABI 1.18) is the
+ * one call that does not take that mutex: it may run while another thread is
+ * inside a call on the context.
  *
  * Errors: 0 = HM_OK; negative codes below; hm_strerror() describes them.
  * Nothing aborts the process, and a failed GPU scan is reported, never
@@ -154,6 +156,9 @@ typedef struct hm_stats {
                                  are left to the process exit).  `out` is not
                                  written: the caller answers from hm_scan_cpu or
                                  a new context.                                  */
+#define HM_ERR_CANCELLED (-8) /* ABI 1.18: hm_cancel stopped the call.  Nothing is
+                                 written, every launch the call queued has ended
+                                 and the context is fully usable                  */
 
 #define HM_KIND_NONE 0
 #define HM_KIND_GENERIC 1  /* one nonce per lane, generic tail builder          */
@@ -901,6 +906,68 @@ typedef struct hm_find_k_many_stats {
  * it; >= HM_FIND_K_MANY_STATS_SIZE_1_17) of the last successful
  * hm_find_k_many's stats; HM_ERR_INVALID before the first one. */
 int hm_find_k_many_stats_sized(const hm_ctx *ctx, hm_find_k_many_stats *out, size_t size);
+
+/* ---------------------------------------------------------------------------
+ * hm_cancel (ABI 1.18): stop an in-flight find from another thread -- "the job
+ * changed".
+ *
+ * May be called from any thread while another thread is inside a call on `ctx`.
+ * It does not take the context's mutex, makes no HIP call and returns at once:
+ *   1               an hm_find, hm_find_k, hm_find_many or hm_find_k_many call
+ *                   was in flight on ctx and has been signalled
+ *   0               nothing cancellable was in flight: no call at all, a call of
+ *                   another family, or an abandoned context.  Nothing is
+ *                   remembered: a later call is not affected (a cancel meant for
+ *                   the old job never kills the new one)
+ *   HM_ERR_INVALID  ctx == NULL
+ * Racing hm_close with hm_cancel is the caller's error, as racing hm_close with
+ * any other call is.
+ *
+ * A signalled call has one of two outcomes, nothing else:
+ *   HM_ERR_CANCELLED  no output is written (out, found, n, counts untouched, as
+ *                     for any error).  The context is fully usable: every launch
+ *                     the call queued has ended, the next call of any family
+ *                     answers exactly, and no hm_*_stats record of the cancelled
+ *                     family has moved
+ *   HM_OK             its exact answer, when that was already in hand when the
+ *                     call first observed the signal (or it never did)
+ * The signal reaches the GPU inside a running launch: one wave of each
+ * find-family launch relays the context's cancel flag (pinned host memory) to
+ * the launch's stop word, and the kernels' own early exit ends the launch and
+ * every launch queued behind it.  HM_OPT_DEADLINE_MS is
+ * unchanged: it remains the fence for a hung GPU and still abandons the context.
+ *
+ * NOT cancellable in this version: hm_scan*, hm_collect*, hm_verify* and
+ * hm_hash_many.  They are bounded by their range or list and enqueue everything
+ * up front; hm_cancel returns 0 while one runs and it finishes normally.  The
+ * _cpu calls take no context and cannot be cancelled.
+ * ------------------------------------------------------------------------- */
+int hm_cancel(hm_ctx *ctx);
+
+#define HM_CANCEL_FAMILY_NONE 0
+#define HM_CANCEL_FAMILY_FIND 1
+#define HM_CANCEL_FAMILY_FIND_K 2
+#define HM_CANCEL_FAMILY_FIND_MANY 3
+#define HM_CANCEL_FAMILY_FIND_K_MANY 4
+
+/* Cancellation accounting of a context since hm_open.  The struct only grows
+ * at its end. */
+typedef struct hm_cancel_stats {
+    double latency_ms;          /* the last call that returned HM_ERR_CANCELLED:
+                                   from hm_cancel's flag store to that call's
+                                   return (0 before the first one)                */
+    uint64_t cancels;           /* hm_cancel calls that returned 1                */
+    uint64_t cancelled_calls;   /* calls that returned HM_ERR_CANCELLED           */
+    int32_t launches_in_flight; /* of that last call: launches in flight when the
+                                   host first saw the signal                      */
+    int32_t family;             /* of that last call: HM_CANCEL_FAMILY_*          */
+} hm_cancel_stats;
+#define HM_CANCEL_STATS_SIZE_1_18 32 /* ABI 1.18 */
+
+/* Writes at most `size` bytes (pass sizeof the struct as the caller compiled
+ * it; >= HM_CANCEL_STATS_SIZE_1_18).  Like hm_cancel it does not take the
+ * context's mutex; all zeros before the first hm_cancel. */
+int hm_cancel_stats_sized(const hm_ctx *ctx, hm_cancel_stats *out, size_t size);
 
 int hm_set_option(hm_ctx *ctx, int opt, int64_t value);
 

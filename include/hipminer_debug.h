@@ -88,6 +88,13 @@ double hm_debug_auto_deadline_ms(const uint8_t *msg, size_t len, uint64_t lo, ui
  * up to HM_OPT_STREAMS once calls used them; -1 if i is out of range. */
 int hm_debug_streams_made(const hm_ctx *ctx, int i);
 
+/* Test hook of hm_cancel (ABI 1.18).  on != 0: the find-family launches of ctx
+ * get a null cancel pointer (no relay wave) and the host does not test the
+ * cancel flag, so a call that hm_cancel signalled (it still returns 1) runs to
+ * its end: what stops a launch is the relay.  A debug export, not an option id:
+ * the ids of hm_set_option end at 23.  HM_ERR_INVALID for ctx == NULL. */
+int hm_debug_no_relay(hm_ctx *ctx, int on);
+
 /* The planner's digit segments of [lo, hi] for msg: up to `cap` descriptors of
  * 13 x int64 each -- d, lo, hi, kind, W1, V, trailer, straddle, seg_cost
  * (SIMD cycles / 64 nonces), lane3, f, tch, fe (the last three chained only).
