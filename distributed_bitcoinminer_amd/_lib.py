@@ -148,6 +148,15 @@ class hm_find_k_many_stats(_Stats):
                 ("ndev", ctypes.c_int32)]
 
 
+class hm_scan_k_stats(_Stats):
+    """hm_scan_k_stats of include/hipminer.h (ABI 1.19)."""
+    _fields_ = [("wall_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
+                ("nonces", ctypes.c_uint64), ("inserted", ctypes.c_uint64),
+                ("compactions", ctypes.c_uint64), ("launches", ctypes.c_int32),
+                ("ndev", ctypes.c_int32), ("k", ctypes.c_int32),
+                ("count", ctypes.c_int32)]
+
+
 class hm_cancel_stats(_Stats):
     """hm_cancel_stats of include/hipminer.h (ABI 1.18)."""
     _fields_ = [("latency_ms", ctypes.c_double), ("cancels", ctypes.c_uint64),
@@ -217,6 +226,7 @@ class hm_collect_many_stats(_Stats):
 
 HM_COLLECT_CAP_MAX = 1 << 24
 HM_FIND_K_MAX = 1 << 20
+HM_SCAN_K_MAX = 32
 HM_VERIFY_CAP_MAX = 1 << 20
 
 
@@ -226,6 +236,7 @@ def _prototypes() -> dict:
     P = ctypes.POINTER
     i, i64, u64, sz, dbl = (ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_size_t,
                             ctypes.c_double)
+    u32 = ctypes.c_uint32
     ctx, msg, ip, szp, u64p, res = (ctypes.c_void_p, ctypes.c_char_p, P(i), P(sz), P(u64),
                                     P(hm_result))
     rng = [msg, sz, u64, u64]  # msg, len, lo, hi
@@ -252,6 +263,8 @@ def _prototypes() -> dict:
         "hm_find_k_many": (i, [ctx, P(hm_find_k_request), i, res, szp]),
         "hm_find_k_many_cpu": (i, [P(hm_find_k_request), i, i, res, szp]),
         "hm_cancel": (i, [ctx]),
+        "hm_scan_k": (i, [ctx] + rng + [u32, res, szp]),
+        "hm_scan_k_cpu": (i, rng + [u32, i, res, szp]),
         "hm_collect": (i, [ctx] + rng + [u64, res, sz, u64p]),
         "hm_collect_cpu": (i, rng + [u64, i, res, sz, u64p]),
         "hm_collect_many": (i, [ctx, P(hm_collect_request), i, u64p, res, sz, u64p]),
@@ -270,7 +283,7 @@ def _prototypes() -> dict:
     }
     for cls in (hm_stats, hm_find_stats, hm_find_many_stats, hm_find_k_stats,
                 hm_find_k_many_stats, hm_collect_stats, hm_collect_many_stats, hm_verify_stats,
-                hm_verify_many_stats, hm_cancel_stats):
+                hm_verify_many_stats, hm_cancel_stats, hm_scan_k_stats):
         family = "scan" if cls is hm_stats else cls.__name__[3:-6]
         table[f"hm_{family}_stats_sized"] = (i, [ctx, P(cls), sz])
     return table
@@ -438,6 +451,18 @@ class Context:
     def find_k_stats(self) -> dict:
         """hm_find_k_stats_sized: work accounting of the last find_k on this context."""
         return self._stats("hm_find_k_stats_sized", hm_find_k_stats)
+
+    def scan_k(self, msg, lo: int, hi: int, k: int):
+        """hm_scan_k (ABI 1.19): the min(k, nonces of the range) lexicographically
+        smallest (hash, nonce) pairs of the inclusive [lo, hi], ascending; the
+        first is Context.scan's answer.  1 <= k <= HM_SCAN_K_MAX; the whole
+        range is hashed."""
+        return _scan_k(lambda m, kk, out, n: self._lib.hm_scan_k(
+            self._h, m, len(m), lo, hi, kk, out, n), "hm_scan_k", msg, k)
+
+    def scan_k_stats(self) -> dict:
+        """hm_scan_k_stats_sized: work accounting of the last scan_k on this context."""
+        return self._stats("hm_scan_k_stats_sized", hm_scan_k_stats)
 
     def find_k_many(self, requests):
         """hm_find_k_many (ABI 1.17) over [(msg, lo, hi, target, k), ...]: for
@@ -639,6 +664,30 @@ def find_k_cpu(msg, lo: int, hi: int, target: int, k: int, threads: int = 0):
     """hm_find_k_cpu (ABI 1.16): Context.find_k's answer on the host's cores."""
     return _find_k(lambda m, out, n: load().hm_find_k_cpu(
         m, len(m), lo, hi, target, k, threads, out, n), "hm_find_k_cpu", msg, k)
+
+
+def _scan_k(call, what: str, msg, k: int):
+    """Run a scan_k entry point with a buffer of k records and shape its
+    answer: a list of (hash, nonce).  A k the ABI refuses goes through with no
+    buffer (k as 0 when it does not fit 32 bits), so the library refuses it."""
+    m = as_bytes(msg)
+    valid = 0 < k <= HM_SCAN_K_MAX
+    buf = (hm_result * k)() if valid else None
+    n = ctypes.c_size_t(0)
+    rc = call(m, k if 0 <= k < 1 << 32 else 0, buf, ctypes.byref(n))
+    if rc != HM_OK:
+        raise _error(rc, what)
+    t = int(n.value)
+    if t == 0:
+        return []
+    words = struct.unpack_from(f"={2 * t}Q", buf)
+    return list(zip(words[0::2], words[1::2]))
+
+
+def scan_k_cpu(msg, lo: int, hi: int, k: int, threads: int = 0):
+    """hm_scan_k_cpu (ABI 1.19): Context.scan_k's answer on the host's cores."""
+    return _scan_k(lambda m, kk, out, n: load().hm_scan_k_cpu(
+        m, len(m), lo, hi, kk, threads, out, n), "hm_scan_k_cpu", msg, k)
 
 
 def find_k_requests(requests):

@@ -34,7 +34,9 @@
 //   (batch.cpp); fused_tasks.hpp has the fused batch kernels' task walker
 //   (hm_fused_find_kernel runs on it).  hm_cancel (ABI 1.18): cancel.hpp, the
 //   flag's state machine; cancel_relay.hpp, the relay wave of the four
-//   find-family kernel files.  hm_find and hm_find_k share one
+//   find-family kernel files.  hm_scan_k (ABI 1.19): scan_k.cpp over
+//   hm_collect's walk, the kernels of scan_k_kernels.hip, a fold launch behind
+//   each scan launch.  hm_find and hm_find_k share one
 //   early-exit walk (find_walk), every family's stats getter is stats_out over
 //   its StatsSlot of hm_ctx (both hm_internal.hpp), and guarded() and the
 //   null-message rule (msg_or_empty) are plan.hpp's, shared with host_scan.cpp.
@@ -76,7 +78,8 @@ uint64_t hm_hash(const uint8_t* msg, size_t len, uint64_t nonce) {
 // 1.16: hm_find_k, hm_find_k_cpu, hm_find_k_stats_sized, HM_OPT_FIND_K_BUF
 // 1.17: hm_find_k_many, hm_find_k_many_cpu, hm_find_k_many_stats_sized
 // 1.18: hm_cancel, HM_ERR_CANCELLED, hm_cancel_stats_sized; debug export hm_debug_no_relay
-int hm_version(void) { return (1 << 16) | 18; }
+// 1.19: hm_scan_k, hm_scan_k_cpu, hm_scan_k_stats_sized
+int hm_version(void) { return (1 << 16) | 19; }
 
 // The digest of the sources this library was built from (build_id.py), kept
 // in the binary behind a tag so tools can read it without loading the library.
@@ -377,6 +380,23 @@ int hm_collect(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_
 
 int hm_collect_stats_sized(const hm_ctx* ctx, hm_collect_stats* out, size_t size) {
     return stats_out(ctx, &hm_ctx::collect_stats, out, size, HM_COLLECT_STATS_SIZE_1_11);
+}
+
+int hm_scan_k(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, uint32_t k,
+              hm_result* out, size_t* n) {
+    if (!ctx || !out || !n || (!msg && len) || k == 0 || k > HM_SCAN_K_MAX) return HM_ERR_INVALID;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    std::vector<hm_result> recs;
+    int rc = guarded([&] { return scan_k_locked(ctx, msg, len, lo, hi, k, &recs); });
+    if (rc) return rc;
+    // nothing at or beyond out[*n] is touched
+    if (!recs.empty()) memcpy(out, recs.data(), recs.size() * sizeof(hm_result));
+    *n = recs.size();
+    return HM_OK;
+}
+
+int hm_scan_k_stats_sized(const hm_ctx* ctx, hm_scan_k_stats* out, size_t size) {
+    return stats_out(ctx, &hm_ctx::scan_k_stats, out, size, HM_SCAN_K_STATS_SIZE_1_19);
 }
 
 int hm_collect_many(hm_ctx* ctx, const hm_collect_request* reqs, int n, uint64_t* totals,

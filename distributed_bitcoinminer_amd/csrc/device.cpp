@@ -109,6 +109,8 @@ void device_free(Device& dv) {
     if (dv.collect_ctl) (void)hipFree(dv.collect_ctl);
     if (dv.collect_buf) (void)hipFree(dv.collect_buf);
     if (dv.collect_many_ctl) (void)hipFree(dv.collect_many_ctl);
+    if (dv.scan_k_ctl) (void)hipFree(dv.scan_k_ctl);
+    if (dv.scan_k_waves) (void)hipFree(dv.scan_k_waves);
     if (dv.collect_tags) (void)hipFree(dv.collect_tags);
     if (dv.verify_ctl) (void)hipFree(dv.verify_ctl);
     if (dv.verify_in) (void)hipFree(dv.verify_in);

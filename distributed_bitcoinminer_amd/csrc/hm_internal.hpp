@@ -9,6 +9,7 @@
 //   find.cpp      hm_find; the early-exit walk's steps (find_walk, below, runs them)
 //   find_k.cpp    hm_find_k, over the same walk
 //   collect.cpp   hm_collect
+//   scan_k.cpp    hm_scan_k
 //   batch.cpp     the chunk runner of the three batch calls below: plan, prepare, launch, wait and read
 //   find_many.cpp hm_find_many
 //   find_k_many.cpp hm_find_k_many
@@ -148,6 +149,11 @@ struct Device {
     size_t vm_ctl_words = 0;
     uint64_t* vm_refs = nullptr;
     size_t vm_refs_cap = 0;
+    // hm_scan_k, both made on first use: the kSkWords control words and device list (kernels.hpp
+    // ScanKArgs), and the wave-list buffer: kMaxCandWaves slots of kScanKMax records, then the
+    // kMaxCandWaves 32-bit counts
+    uint64_t* scan_k_ctl = nullptr;
+    uint64_t* scan_k_waves = nullptr;
     hm_result* host_out = nullptr; // pinned, fine-grained [kMaxBatch]: the 16-B readback slots
     // hm_cancel: this device's pointer to the context's cancel flag (hm_ctx::cancel.flag)
     uint32_t* cancel_dev = nullptr;
@@ -233,6 +239,7 @@ struct hm_ctx {
     hm::StatsSlot<hm_collect_many_stats> collect_many_stats;
     hm::StatsSlot<hm_find_k_stats> find_k_stats;
     hm::StatsSlot<hm_find_k_many_stats> find_k_many_stats;
+    hm::StatsSlot<hm_scan_k_stats> scan_k_stats;
 };
 
 namespace hm {
@@ -286,8 +293,8 @@ void list_deadline(hm_ctx* ctx, size_t n, std::chrono::steady_clock::time_point 
 
 // ---- seg_walk.cpp ----
 // Which kernels run a segment: the scan's, its checked variants, hm_find's,
-// hm_collect's or hm_find_k's.
-enum class Family { Scan, ScanCsum, Find, Collect, FindK };
+// hm_collect's, hm_find_k's or hm_scan_k's.
+enum class Family { Scan, ScanCsum, Find, Collect, FindK, ScanK };
 // The kernel of `family` for a segment of `kind` (s: the tiled instantiation's
 // template arguments; unused otherwise): its mangled name in
 // hipminer_scan.hsaco and the name rocprofv3 prints (sans arguments).
@@ -333,8 +340,8 @@ struct SegStep {
     uint32_t unit0;
 };
 // What follows a step's argument block in the kernel's parameter: nothing
-// (scan), FindArgs, CollectArgs or FindKArgs -- the layout of kernels.hpp's
-// Find*Args, Collect*Args and FindK*Args.
+// (scan), FindArgs, CollectArgs, FindKArgs or ScanKArgs -- the layout of
+// kernels.hpp's Find*Args, Collect*Args, FindK*Args and ScanK*Args.
 struct NoTrailer {};
 template <typename Base, typename Trailer>
 struct WithTrailer {
@@ -349,7 +356,10 @@ static_assert(sizeof(WithTrailer<TiledArgs, FindArgs>) == sizeof(FindTiledArgs) 
               sizeof(WithTrailer<GenericArgs, CollectArgs>) == sizeof(CollectGenericArgs) &&
               sizeof(WithTrailer<TiledArgs, FindKArgs>) == sizeof(FindKTiledArgs) &&
               sizeof(WithTrailer<ChainedArgs, FindKArgs>) == sizeof(FindKChainedArgs) &&
-              sizeof(WithTrailer<GenericArgs, FindKArgs>) == sizeof(FindKGenericArgs));
+              sizeof(WithTrailer<GenericArgs, FindKArgs>) == sizeof(FindKGenericArgs) &&
+              sizeof(WithTrailer<TiledArgs, ScanKArgs>) == sizeof(ScanKTiledArgs) &&
+              sizeof(WithTrailer<ChainedArgs, ScanKArgs>) == sizeof(ScanKChainedArgs) &&
+              sizeof(WithTrailer<GenericArgs, ScanKArgs>) == sizeof(ScanKGenericArgs));
 
 // A resumable cursor over the launches of one segment on one device and
 // stream.  Generic segments run in chunks of `generic_chunk` nonces; tiled ones
@@ -773,6 +783,9 @@ int find_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64
 int find_many_locked(hm_ctx* ctx, const hm_find_request* reqs, int n, hm_result* outs, int* found);
 int collect_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
                    uint64_t target, size_t cap, std::vector<hm_result>* recs, uint64_t* total);
+// hm_scan_k: *recs = the min(k, nonces of [lo, hi]) lowest (hash, nonce) pairs, ascending.
+int scan_k_locked(hm_ctx* ctx, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi,
+                  uint32_t k, std::vector<hm_result>* recs);
 // hm_collect_many: (*totals)[i] for i < n, *total their sum, and *recs (every
 // record, request-major, ascending by nonce inside a request) when *total <=
 // cap; empty otherwise.

@@ -4,8 +4,9 @@
 // the min-hash scan, the first-below-target search (ABI 1.10) and its batch
 // form (ABI 1.13), the all-below-target collection (ABI 1.11) and its batch
 // form (ABI 1.15), the recheck of a list (ABI 1.12) and of the lists of many
-// messages (ABI 1.14) and the k-lowest-below-target search (ABI 1.16), on the
-// host's cores.
+// messages (ABI 1.14), the k-lowest-below-target search (ABI 1.16) and
+// hm_scan_k_cpu, the k lowest hashes of a range (ABI 1.19), on the host's
+// cores.
 //
 // SURVEY §8(b)'s liveness path.  The reference miner always answers a
 // Request with a Result (cmu440/bitcoin/miner/miner.go:60-62); a GPU miner
@@ -294,6 +295,36 @@ void collect_chunk(const MsgPlan& mp, uint64_t a, uint64_t b, uint64_t target, s
     } catch (...) {
         out->failed = true;
     }
+}
+
+// hm_scan_k_cpu's share of one thread: the k lowest (key, nonce) records of its
+// contiguous chunk, ascending.  A full list is tested against its k-th record
+// first -- one compare per nonce, as the running minimum's -- and only a record
+// lexicographically below it is inserted.
+struct LowK {
+    hm_result rec[HM_SCAN_K_MAX] = {};
+    uint32_t cnt = 0;
+    void take(uint32_t k, uint64_t key, uint64_t n) {
+        if (cnt == k) {
+            const hm_result& last = rec[k - 1];
+            if (key > last.hash || (key == last.hash && n > last.nonce)) return;
+        }
+        uint32_t i = cnt < k ? cnt++ : k - 1;
+        for (; i > 0 && (key < rec[i - 1].hash || (key == rec[i - 1].hash && n < rec[i - 1].nonce));
+             --i)
+            rec[i] = rec[i - 1];
+        rec[i] = hm_result{key, n};
+    }
+};
+
+void scan_k_chunk(const MsgPlan& mp, uint64_t a, uint64_t b, uint32_t k, CompressFn compress,
+                  LowK* out) {
+    LowK low;
+    walk_chunk(mp, a, b, compress, [&](uint64_t key, uint64_t n) {
+        low.take(k, key, n);
+        return false;
+    });
+    *out = low;
 }
 
 // Hash(msg, n) of one nonce from the midstate: the tail bytes of walk_chunk,
@@ -644,6 +675,36 @@ extern "C" int hm_collect_cpu(const uint8_t* msg, size_t len, uint64_t lo, uint6
             }
         }
         *total = sum;
+        return HM_OK;
+    });
+}
+
+extern "C" int hm_scan_k_cpu(const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, uint32_t k,
+                             int threads, hm_result* out, size_t* n) {
+    using namespace hm;
+    if (!out || !n || (!msg && len) || k == 0 || k > HM_SCAN_K_MAX) return HM_ERR_INVALID;
+    return guarded([&] {
+        if (lo > hi) {
+            *n = 0;
+            return HM_OK;
+        }
+        const MsgPlan mp = plan_message(msg_or_empty(msg, len));
+        const CompressFn compress = pick_compress();
+        // contiguous, near-equal chunks, as hm_scan_cpu's; the k lowest of the
+        // chunks' lists are the k lowest of the range
+        std::vector<LowK> part;
+        const int rc = over_range(
+            lo, hi, threads, [&](unsigned parts) { part.resize(parts); },
+            [&](unsigned t, uint64_t a, uint64_t b) {
+                scan_k_chunk(mp, a, b, k, compress, &part[t]);
+            });
+        if (rc) return rc;
+        LowK all;
+        for (const LowK& p : part)
+            for (uint32_t i = 0; i < p.cnt; ++i) all.take(k, p.rec[i].hash, p.rec[i].nonce);
+        // nothing at or beyond out[*n] is touched
+        memcpy(out, all.rec, all.cnt * sizeof(hm_result));
+        *n = all.cnt;
         return HM_OK;
     });
 }

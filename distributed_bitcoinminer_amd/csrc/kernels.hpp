@@ -340,6 +340,52 @@ struct FusedFindKArgs {
 static_assert(kFkCursor == kFkStop + 1, "the planner's (MaxUint64, 0) seed serves stop and cursor");
 
 // ---------------------------------------------------------------------------
+// hm_scan_k (scan_k_kernels.hip): the k lowest (hash, nonce)
+// pairs of a range, the whole range hashed.  Per device a control block `ctl`
+// of kSkWords words -- the first kSkZeroed of them zeroed on the stream before
+// a call's first launch -- followed by the device list (kScanKMax records of
+// 2 x u64, sorted), and a wave-list buffer: one slot of kScanKMax records and
+// one count per wave of a launch.  Every wave writes its slot before its
+// kernel ends; hm_scan_k_fold_kernel, enqueued behind each launch, merges the
+// launch's wave lists into the device list and refreshes the carried bound.
+// The scan_k kernels take the scan kernel's argument block (cand and sums
+// unused) plus this one.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kScanKMax = 32;  // HM_SCAN_K_MAX
+constexpr int kSkCount = 0;        // 0; records in the device list (<= k)
+constexpr int kSkBoundKey = 1;     // the carried bound, the device list's k-th record:
+constexpr int kSkBoundNonce = 2;   //   valid if and only if count == k
+constexpr int kSkInserted = 3;     // 0; += records that passed a wave's bound, once per wave
+constexpr int kSkCompactions = 4;  // 0; += a wave's compactions, once per wave
+constexpr int kSkZeroed = 5;
+constexpr int kSkList = 8;         // the device list: kScanKMax x (hash, nonce)
+constexpr int kSkWords = kSkList + 2 * (int)kScanKMax;
+struct ScanKArgs {
+    uint64_t* ctl;        // the device's kSkWords words
+    uint64_t* wave_recs;  // [kMaxCandWaves][kScanKMax] records of 2 x u64
+    uint32_t* wave_cnt;   // [kMaxCandWaves]: records in each wave's slot
+    uint32_t k;           // 1 .. kScanKMax
+};
+struct ScanKTiledArgs {
+    TiledArgs t;
+    ScanKArgs k;
+};
+struct ScanKChainedArgs {
+    ChainedArgs c;
+    ScanKArgs k;
+};
+struct ScanKGenericArgs {
+    GenericArgs g;
+    ScanKArgs k;
+};
+// hm_scan_k_fold_kernel: one workgroup behind each launch, over the `nwaves`
+// wave slots that launch wrote.
+struct ScanKFoldArgs {
+    ScanKArgs k;
+    uint32_t nwaves;  // <= kMaxCandWaves
+};
+
+// ---------------------------------------------------------------------------
 // hm_hash_many / hm_verify (verify_kernels.hip, DESIGN.md "Recheck a list"):
 // Hash(msg, nonce) for a LIST of arbitrary nonces, one element per lane, each
 // lane with its own digit count and tail layout.  hm_hash_list_kernel<false>

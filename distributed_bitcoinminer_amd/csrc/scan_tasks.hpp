@@ -1,6 +1,6 @@
 // scan_tasks.hpp -- one task of each scan kernel kind, shared by the
 // per-segment kernels (scan_kernels.hip, find_kernels.hip,
-// collect_kernels.hip, find_k_kernels.hip) and the fused small-request kernel
+// collect_kernels.hip, find_k_kernels.hip, scan_k_kernels.hip) and the fused small-request kernel
 // (fused_kernels.hip): the reductions a task folds its nonces into, the task
 // dispenser, the decoding of a task id, the list of tiled layouts and the
 // task bodies.
@@ -209,6 +209,136 @@ DEV void take_step(WaveFirstK& f, bool cand, uint32_t h0, uint32_t h1, uint64_t 
     }
 }
 
+// "The k lowest" reduction (scan_k_kernels.hip, hm_scan_k): the wave keeps a
+// list of up to 64 (hash, nonce) records in its own 1 KiB of LDS and, once it
+// knows k of them, a wave-uniform bound (key, nonce) that every later record
+// must lie strictly below.  The per-nonce test is h0 <= bhi, WaveBest's one
+// compare (bhi = 0xffffffff while unbounded).  Behind the ballot the 64-bit
+// key, the range check, lane_ok and (key, nonce) < bound are formed, and the
+// hit lanes append at cnt + their rank among the hit lanes.  A list that
+// cannot take a step's hits is compacted first (lowk_compact): sorted, cut to
+// its k lowest records, and the bound lowered to the k-th of them.  All the
+// state but the list is wave-uniform (SGPRs).
+struct WaveLowK {
+    uint32_t bhi = 0xffffffffu;  // bound key >> 32 while bounded
+    uint64_t bkey = ~0ull, bnonce = ~0ull;  // the bound (bounded only)
+    bool bounded = false;
+    uint32_t cnt = 0;  // records in the list
+    uint32_t k;
+    uint64_t* list;    // LDS: 64 slots of 2 x u64, this wave's own
+    uint64_t inserted = 0;     // records appended (stats)
+    uint32_t compactions = 0;  // (stats)
+};
+// (the builtin returns int: each half goes through uint32_t, or the low one
+// would sign-extend into the high one)
+DEV uint64_t readlane64(uint64_t x, uint32_t lane) {
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((uint32_t)(x >> 32), lane);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((uint32_t)x, lane);
+    return ((uint64_t)hi << 32) | lo;
+}
+// The lane id, formed where it is used: everything this reduction does per
+// lane sits behind the ballot, and a lane id the compiler may hoist (with the
+// list address and the lane's bit mask derived from it) would live in VGPRs
+// through the task bodies' hot loop.  The empty asm pins it to its block.
+DEV uint32_t cold_lane_id() {
+    uint32_t zero = 0;
+    asm volatile("" : "+v"(zero));
+    return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, zero));
+}
+DEV bool lex_below(uint64_t k, uint64_t n, uint64_t k2, uint64_t n2) {
+    return k < k2 || (k == k2 && n < n2);
+}
+// Sort the list, keep its min(cnt, k) lowest records, lower the bound.  Lane i
+// < cnt holds record i; its rank is the number of list records below it (the
+// records are distinct by nonce, so the ranks are a permutation of 0..cnt-1);
+// ranks < k go back to slot = rank.
+DEV void lowk_compact(WaveLowK& w) {
+    const uint32_t lane = cold_lane_id();
+    const bool have = lane < w.cnt;
+    uint64_t key = ~0ull, nn = ~0ull;
+    if (have) {
+        key = w.list[2 * lane];
+        nn = w.list[2 * lane + 1];
+    }
+    // all 64 lanes, unrolled (constant lane selects): a lane at or past cnt
+    // holds (MaxUint64, MaxUint64), which is below no record, so it adds to
+    // no rank.  That pair is also a representable record (nonce 2^64-1
+    // hashing to 2^64-1).  Such a record still ranks correctly: every other
+    // record is below it, and an empty lane's equal pair is not (the test is
+    // strict), so its rank is cnt - 1, the last.  Unrolled, so that the task
+    // bodies' hot loop keeps no loop inside it (align_loops.py places the
+    // innermost one)
+    uint32_t rank = 0;
+#pragma unroll
+    for (int j = 0; j < kWaveSize; ++j)
+        rank += lex_below(readlane64(key, j), readlane64(nn, j), key, nn) ? 1u : 0u;
+    __builtin_amdgcn_wave_barrier();  // every lane holds its record before any slot is rewritten
+    if (have && rank < w.k) {
+        w.list[2 * rank] = key;
+        w.list[2 * rank + 1] = nn;
+    }
+    __builtin_amdgcn_wave_barrier();
+    ++w.compactions;
+    if (w.cnt >= w.k) {
+        w.cnt = w.k;
+        // the k-th lowest: the one lane of rank k - 1
+        const uint64_t kth = __builtin_amdgcn_ballot_w64(have && rank == w.k - 1);
+        const uint32_t src = (uint32_t)__builtin_ctzll(kth);
+        const uint64_t bk = readlane64(key, src), bn = readlane64(nn, src);
+        if (!w.bounded || lex_below(bk, bn, w.bkey, w.bnonce)) {
+            w.bkey = bk;
+            w.bnonce = bn;
+            w.bhi = (uint32_t)(bk >> 32);
+            w.bounded = true;
+        }
+    }
+}
+// Append the records of the lanes in `mask` (a ballot; at most 64 - cnt lanes);
+// `in` is the lane's own bit of it.
+DEV void lowk_append(WaveLowK& w, uint64_t mask, bool in, uint64_t key, uint64_t nn) {
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
+                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    if (in) {
+        const uint32_t slot = w.cnt + rank;
+        w.list[2 * slot] = key;
+        w.list[2 * slot + 1] = nn;
+    }
+    __builtin_amdgcn_wave_barrier();
+    w.cnt += (uint32_t)__builtin_popcountll(mask);
+}
+// Insert the records of the lanes in `hits` (a non-empty ballot; `ok` is the
+// lane's own bit of it).  If they do
+// not fit into the 64 slots the list is compacted first (then cnt <= k <= 32);
+// if they still do not fit they go in as two halves of at most 32 lanes with a
+// compaction between.  A compaction may lower the bound below a hit that is
+// still to be appended: it is appended all the same and leaves with the next
+// compaction.
+DEV void lowk_insert(WaveLowK& w, bool ok, uint64_t hits, uint64_t key, uint64_t nn) {
+    const uint32_t n = (uint32_t)__builtin_popcountll(hits);
+    w.inserted += n;
+    if (w.cnt + n > (uint32_t)kWaveSize) lowk_compact(w);
+    if (w.cnt + n > (uint32_t)kWaveSize) {
+        const bool low_half = cold_lane_id() < 32u;
+        lowk_append(w, hits & 0xffffffffull, ok && low_half, key, nn);
+        lowk_compact(w);
+        lowk_append(w, hits & ~0xffffffffull, ok && !low_half, key, nn);
+    } else {
+        lowk_append(w, hits, ok, key, nn);
+    }
+}
+DEV bool wave_cand(const WaveLowK& w, uint32_t h0) { return h0 <= w.bhi; }
+DEV void take_step(WaveLowK& w, bool cand, uint32_t h0, uint32_t h1, uint64_t nbase, uint32_t off,
+                   uint64_t seg_lo, uint64_t seg_hi, bool lane_ok) {
+    if (__builtin_amdgcn_ballot_w64(cand)) {
+        const uint64_t key = ((uint64_t)h0 << 32) | h1;
+        const uint64_t nn = nbase + off;
+        const bool ok = cand && lane_ok && nn >= seg_lo && nn <= seg_hi &&
+                        (!w.bounded || lex_below(key, nn, w.bkey, w.bnonce));
+        const uint64_t hits = __builtin_amdgcn_ballot_w64(ok);
+        if (hits) lowk_insert(w, ok, hits, key, nn);
+    }
+}
+
 // The wave's count into the device total, once, at the wave's exit
 // (hm_collect's hits, hm_verify's bad records).
 DEV void wave_total(uint64_t* total, uint64_t count) {
@@ -375,8 +505,8 @@ DEV uint64_t lane_digits(uint32_t v, uint32_t q) {
 // per-segment kernels take the constant defaults, so their loop is the full
 // one).  Best is the reduction the task folds its nonces into: WaveBest (the
 // running minimum, the default), WaveFirst (hm_find), WaveCollect
-// (hm_collect) or WaveFirstK (hm_find_k); each brings its wave_cand (the one compare per nonce) and
-// take_step.
+// (hm_collect), WaveFirstK (hm_find_k) or WaveLowK (hm_scan_k); each brings its wave_cand (the
+// one compare per nonce) and take_step.
 // ---------------------------------------------------------------------------
 template <int W1, bool STRADDLE, bool TRAILER, bool CSUM, typename S0, typename KW,
           typename Best = WaveBest>

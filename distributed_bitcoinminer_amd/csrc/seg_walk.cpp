@@ -14,10 +14,12 @@ KernelName kernel_name(Family family, int kind, const SegPlan* s) {
     const char* pre = family == Family::Find      ? "find_"
                       : family == Family::Collect ? "collect_"
                       : family == Family::FindK   ? "find_k_"
+                      : family == Family::ScanK   ? "scan_k_"
                                                   : "";
     const char* arg_pre = family == Family::Find      ? "Find"
                           : family == Family::Collect ? "Collect"
                           : family == Family::FindK   ? "FindK"
+                          : family == Family::ScanK   ? "ScanK"
                                                       : "";
     std::string fn = std::string("hm_") + pre + layouts[li] +
                      (family == Family::ScanCsum ? "_csum" : "") + "_kernel";

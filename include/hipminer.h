@@ -23,6 +23,8 @@
  * that exchange, which the reference's server lacks (server.go:273 believes
  * the hash it is sent): the hash at every nonce of a list, and which
  * (hash, nonce) records of a list are wrong or not below a target.
+ * hm_scan_k (ABI 1.19) is the ranking form: the k lowest (hash, nonce) pairs
+ * of a range, the reference's minimum being k = 1.
  *
  * The cgo binding a maintainer adds to the Go miner is in INTEGRATION.md.
  *
@@ -968,6 +970,71 @@ typedef struct hm_cancel_stats {
  * it; >= HM_CANCEL_STATS_SIZE_1_18).  Like hm_cancel it does not take the
  * context's mutex; all zeros before the first hm_cancel. */
 int hm_cancel_stats_sized(const hm_ctx *ctx, hm_cancel_stats *out, size_t size);
+
+/* ---------------------------------------------------------------------------
+ * hm_scan_k (ABI 1.19): the k lowest hashes of a range in one pass -- the
+ * runner-ups of a round, the best k shares, the winner audited against the
+ * next-best.  The reference's loop (miner.go:46-59) is k = 1.
+ *
+ *   *n = min(k, number of nonces in the inclusive [lo, hi])
+ *   out[0 .. *n) holds the *n lexicographically smallest (Hash(msg, nonce),
+ *   nonce) pairs of the range, ascending in that order: ties in the hash go
+ *   to the lower nonce, as in hm_scan.  Nothing at or beyond out[*n] is
+ *   touched.  On a non-empty range out[0] is bit for bit hm_scan's answer.
+ *
+ * lo > hi gives *n = 0 and leaves `out` unwritten.  Every nonce is eligible,
+ * UINT64_MAX included.  The whole range is always hashed: there is no target
+ * and no early exit, and the answer never depends on dispatch order.
+ *
+ * HM_ERR_INVALID: k == 0, k > HM_SCAN_K_MAX, out or n NULL, msg == NULL with
+ * len > 0.  `out` and `*n` are written only on HM_OK.  An abandoned context
+ * returns HM_ERR_TIMEOUT.  HM_OPT_DEADLINE_MS applies as it does for
+ * hm_collect; HM_OPT_FORCE_GENERIC and HM_OPT_GRID_PER_CU are honoured; the
+ * stream, fused and RCCL options do not apply.  The call is not cancellable:
+ * hm_cancel returns 0 while it runs, as for hm_scan and hm_collect.
+ *
+ * Every launch of every device is enqueued on its stream 0 before the host
+ * waits on any, each followed by a small fold launch that merges the
+ * launch's per-wave lists into the device's list of k; the devices' shards
+ * are hm_collect's.  The host merges the devices' lists and rechecks every
+ * record it returns (hash recomputed, nonce in range, order strict): a
+ * record that fails is HM_ERR_INTERNAL.  Each device keeps a 16 MiB wave-list
+ * buffer, made on the first hm_scan_k and kept until hm_close.  For k >
+ * HM_SCAN_K_MAX use hm_collect at a target.  hm_scan_k does not change what
+ * any other family's stats call reports. */
+#define HM_SCAN_K_MAX 32u
+int hm_scan_k(hm_ctx *ctx, const uint8_t *msg, size_t len, uint64_t lo, uint64_t hi,
+              uint32_t k, hm_result *out, size_t *n);
+
+/* The same answer as hm_scan_k on the host's cores, no GPU (`threads` as
+ * hm_scan_cpu's; 0 = the hardware threads).  Each thread keeps the k lowest
+ * of its contiguous chunk; the lists are merged at the end. */
+int hm_scan_k_cpu(const uint8_t *msg, size_t len, uint64_t lo, uint64_t hi, uint32_t k,
+                  int threads, hm_result *out, size_t *n);
+
+/* Work accounting of the most recent successful hm_scan_k on a context.  The
+ * struct only grows at its end. */
+typedef struct hm_scan_k_stats {
+    double wall_ms;       /* host wall time of the call                          */
+    double kernel_ms;     /* HIP-event time from each device's first launch to
+                             the end of its last fold, summed over devices       */
+    uint64_t nonces;      /* nonces covered by the launches: hi - lo + 1         */
+    uint64_t inserted;    /* device-side: records that passed a wave's bound and
+                             entered its list, summed at wave exit.  Far below
+                             `nonces` on a large range: the bound at work        */
+    uint64_t compactions; /* device-side: list compactions of the scan waves,
+                             each wave's last one included                       */
+    int32_t launches;     /* scan_k-kernel launches issued (each has one fold)   */
+    int32_t ndev;         /* devices of the context                              */
+    int32_t k;            /* the call's k                                        */
+    int32_t count;        /* the call's *n                                       */
+} hm_scan_k_stats;
+#define HM_SCAN_K_STATS_SIZE_1_19 56 /* ABI 1.19 */
+
+/* Writes at most `size` bytes (pass sizeof the struct as the caller compiled
+ * it; >= HM_SCAN_K_STATS_SIZE_1_19) of the last successful hm_scan_k's stats;
+ * HM_ERR_INVALID before the first one. */
+int hm_scan_k_stats_sized(const hm_ctx *ctx, hm_scan_k_stats *out, size_t size);
 
 int hm_set_option(hm_ctx *ctx, int opt, int64_t value);
 
